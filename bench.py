@@ -6,8 +6,23 @@ A "step" is one reference minibatch: pull of the gathered key set, training of
 `--minibatch` lines (learn_instance for every kept position), push of the mean
 gradients with AdaGrad — all on the GPU through libswps.so.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line;
+nothing else.  --full adds everything measured beside the headline: the profiled
+second pass with its per-kernel roofline and exchange accounting, the other
+precision modes, the B = 100 and config-1 legs, the CPU baselines and the
+config-4 / LR / sent2vec legs (each with its own switches below).  --app lr and
+--app s2v are benchmarks of their own and run whole either way.
+
+--dump-outputs DIR writes what the timed steps left behind, right after the
+last of them (before any profiled pass): `table_rows.npy`, a fixed seeded
+sample of the trained table's rows [h | v | h2sum | v2sum] in the table's
+precision; `table_keys.npy`, their 64-bit keys as float64 pairs (high, low 32
+bits), in ascending key order; `stats.npy`, the learner's cumulative counters
+(DUMP_STATS) as float64.  Ranks above 0 append `_rank<r>` to the names.  The
+inputs are seeded, so equal arguments give equal arrays on equal code.
 
 N > 1: every rank trains its own corpus of the same size (the reference's
 per-rank local data) and serves the keys BasicHashFrag assigns to it; each
@@ -430,12 +445,35 @@ def exchange_block(xs, steps, step_s, world, note):
             "GBps": xg, "peak": XGMI_PEAK_GBS, "frac": xg / XGMI_PEAK_GBS, "world": world, "note": note}
 
 
+DUMP_BYTES = 60 * 10 ** 6  # --dump-outputs: the sampled rows' share of the 64 MB allowed in all
+DUMP_STATS = ("batches", "kept", "words", "pairs", "pulled", "pushed", "ctx_rows", "tgt_rows")
+
+
+def dump_outputs(dirname, rank, world, t, w):
+    """--dump-outputs: a seeded sample of the rows this rank's table holds after the timed steps
+    (ascending key order; the byte budget shared among the ranks), their keys and the learner's
+    counters, as .npy files."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    held = np.sort(t.keys())
+    n = min(len(held), DUMP_BYTES // world // (t.row_elems * (8 if t.dtype == "f64" else 4)))
+    pick = np.sort(np.random.default_rng(20240).choice(len(held), n, replace=False))
+    k = held[pick]
+    rows = t.export(torch.as_tensor(k.astype(np.int64), device=torch.device("cuda", t.device))).cpu().numpy()
+    st = w.stats()
+    sfx = "" if rank == 0 else "_rank%d" % rank
+    np.save(os.path.join(dirname, "table_rows%s.npy" % sfx), rows)
+    np.save(os.path.join(dirname, "table_keys%s.npy" % sfx),
+            np.stack([(k >> np.uint64(32)).astype(np.float64), (k & np.uint64(0xffffffff)).astype(np.float64)], axis=1))
+    np.save(os.path.join(dirname, "stats%s.npy" % sfx), np.array([float(st.get(s, 0)) for s in DUMP_STATS]))
+
+
 def w2v_leg(sw, ctx, args, ids, off, keys, prec, minibatch, dim, frag_num, steps, warmup, tokens, vocab,
-            profile=True, setup_s=None):
+            profile=True, setup_s=None, dump=None):
     """Build a CBOW-NS context on this rank's corpus (key-sharded over ctx's communicator when
     ctx.sharded, else one HBM shard), warm up, time `steps` minibatches (barrier + sync on both
-    sides, max over ranks), then a second, profiled pass for the per-kernel roofline.  Returns
-    the leg's raw measurements."""
+    sides, max over ranks), write the trained rows to `dump` if given, then (profile) a second,
+    profiled pass for the per-kernel roofline.  Returns the leg's raw measurements."""
     kw = dict(window=args.window, negative=args.negative, minibatch=minibatch, sample=args.sample, alpha=args.alpha,
               profile=False, fp64_intermediates=INTER[prec], sampler=args.sampler)
     t = sw.Table("w2v", dim=dim, capacity=vocab, dtype=args.dtype, learning_rate=args.lr, device=ctx.local,
@@ -474,6 +512,8 @@ def w2v_leg(sw, ctx, args, ids, off, keys, prec, minibatch, dim, frag_num, steps
 
     dt, d = timed(steps)                    # the measured region: no event timing inside
     res = {"dt": dt, "d": d, "info": info, "steps": steps, "warmup": warmup}
+    if dump:
+        dump_outputs(dump, ctx.rank, ctx.world, t, w)
     if profile:
         w.set_profile(True)                 # a second, profiled pass for the per-kernel roofline
         w.kernel_times(reset=True)
@@ -659,6 +699,13 @@ def main():
                     help="concurrent single-threaded oracle processes for the w2v cpu_baseline (host cores used)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline's timed steps: its profiled pass (roofline, kernel_ms, exchange), the "
+                         "other precision modes, the B = 100 and config-1 legs, the CPU baselines and the config-4, "
+                         "LR and sent2vec legs (the --no-* / --*-steps switches below choose among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a seeded sample of the trained table rows, their keys and "
+                         "the learner's counters to DIR/<name>.npy (float32 / float64, under 64 MB in all)")
     ap.add_argument("--dim", type=int, default=300)
     ap.add_argument("--window", type=int, default=5)
     ap.add_argument("--negative", type=int, default=5)
@@ -728,6 +775,8 @@ def main():
         args.precision = "parity"
     arm_deadline(int(os.environ.get("RANK", "0")))
     if args.app != "w2v":
+        if args.dump_outputs:
+            ap.error("--dump-outputs writes the headline's (--app w2v) trained rows only")
         return bench_other(args)
 
     import swiftmpi_amd as sw
@@ -742,11 +791,12 @@ def main():
     prec = args.precision
     setup_s = {}
     r = w2v_leg(sw, ctx, args, ids, off, keys, prec, args.minibatch, args.dim, args.frag_num, args.steps,
-                args.warmup, args.tokens, args.vocab, setup_s=setup_s)
+                args.warmup, args.tokens, args.vocab, profile=args.full, setup_s=setup_s, dump=args.dump_outputs)
     dt, total_words = ctx.max_sum(r["dt"], r["d"]["words"])
-    roof = w2v_roofline(r, args, prec, args.minibatch, args.dim, args.tokens, args.vocab, world, ctx.sharded)
+    roof = (w2v_roofline(r, args, prec, args.minibatch, args.dim, args.tokens, args.vocab, world, ctx.sharded)
+            if args.full else None)
     d, info = r["d"], r["info"]
-    one = rank == 0 and world == 1 and not ctx.sharded
+    one = args.full and rank == 0 and world == 1 and not ctx.sharded  # the extra single-GPU legs
 
     # the other precision modes on the same workload, timed the same way
     other_modes = {}
@@ -820,7 +870,7 @@ def main():
                    "pulled_keys_per_step": d["pulled"] / args.steps,
                    "setup_s": dict(setup_s)},
         "roofline": roof,
-        "kernel_ms": {k: v[0] for k, v in r["kt"].items()},
+        "kernel_ms": {k: v[0] for k, v in r["kt"].items()} if args.full else None,
         "other_modes": other_modes or None,
         "minibatch_100": b100_leg,
         "config1": config1,
@@ -837,7 +887,7 @@ def main():
     # BASELINE configs 4, 3 and 5 at their per-GPU shapes beside the headline, at every N (each
     # rank its own share: weak scaling; the same legs at N = 1 give each curve its base point),
     # each with its own roofline, exchange block and (N = 1) CPU baseline
-    if not args.no_app_legs:
+    if args.full and not args.no_app_legs:
         if args.config4_tokens > 0 and args.config4_steps > 0:
             out["config4"] = config4_leg(sw, ctx, args)
         la = argparse.Namespace(**vars(args))
@@ -1289,6 +1339,8 @@ if __name__ == "__main__":
         sys.exit(_rc)
     try:
         main()
+    except SystemExit:  # argparse's own exits (--help, a refused option): its message and code stand
+        raise
     except BaseException as _e:  # noqa: BLE001 — name the rank and phase, and do not hang in teardown
         import traceback
         traceback.print_exc()

@@ -14,6 +14,7 @@ if [ -n "$TESTS" ]; then
   rc=$?; tail -3 gpurun_out/ab_tests.log
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 fi
+BENCH_ARGS="--full $BENCH_ARGS"  # the roofline, B = 100 leg and kernel_ms printed per variant
 IFS=';' read -ra VS <<< "${VARIANTS:-SWPS_FUSED_PUSH=1}"
 for r in $(seq 1 ${REPS:-1}); do
   i=0

@@ -28,7 +28,7 @@ run() {  # name timeout args...
   echo "== $name rc=$rc"; tail -2 "gpurun_out/$name.log" | cut -c1-400
   return $rc
 }
-W2V="bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-parity-leg --b100-steps 0 --config1-steps 0 --no-app-legs"
+W2V="bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-parity-leg --b100-steps 0 --config1-steps 0 --no-app-legs"
 W2VCFG='"app": "w2v", "dim": 300, "dtype": "f32", "world": 1, "line_len": 1000, "sampler": "table"'
 TEXT8='"tokens": 17005207, "vocab": 253854'
 leg() {  # name last(N|launches) config-json args...
@@ -58,7 +58,7 @@ for L in $LEGS; do
     w2v_bfp32) FETCH=1 leg $L 20 "{$W2VCFG, $TEXT8, \"minibatch\": 5000, \"mode\": \"bfp32\", \"sharded\": false}" $W2V ;;
     w2v_bfp40) leg $L 20 "{$W2VCFG, $TEXT8, \"minibatch\": 5000, \"mode\": \"bfp40\", \"sharded\": false}" $W2V --precision bfp40 ;;
     w2v_b100) leg $L 200 "{$W2VCFG, $TEXT8, \"minibatch\": 100, \"mode\": \"bfp32\", \"sharded\": false}" \
-                bench.py --gpus 1 --steps 200 --warmup 10 --minibatch 100 --no-cpu-baseline --no-parity-leg --config1-steps 0 --no-app-legs ;;
+                bench.py --full --gpus 1 --steps 200 --warmup 10 --minibatch 100 --no-cpu-baseline --no-parity-leg --config1-steps 0 --no-app-legs ;;
     w2v_parity) leg $L 20 "{$W2VCFG, $TEXT8, \"minibatch\": 5000, \"mode\": \"parity\", \"sharded\": false}" $W2V --parity ;;
     w2v_fast) leg $L 20 "{$W2VCFG, $TEXT8, \"minibatch\": 5000, \"mode\": \"fast\", \"sharded\": false}" $W2V --precision fast ;;
     lr) leg $L 20 '{"app": "lr", "lr_batch": 65536, "exact": false, "world": 1, "sharded": false, "plan": "none"}' \

@@ -21,7 +21,7 @@ if [ -n "$TESTS" ]; then
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 fi
 if [ -n "$BENCH" ]; then
-  step bench ${BENCH_TIMEOUT:-600} python bench.py ${BENCH_ARGS} || exit $?
+  step bench ${BENCH_TIMEOUT:-600} python bench.py --full ${BENCH_ARGS} || exit $?
   grep '^{' gpurun_out/bench.log > gpurun_out/bench.json || true
 fi
 exit $rc

@@ -3,7 +3,7 @@
 # VARIANTS: ';'-separated env settings for extra sharded runs (e.g. "SWPS_PULL_IN_PLACE=0")
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
-A="--steps 20 --warmup 5 --no-cpu-baseline --no-parity-leg --b100-steps 0 --config1-steps 0"
+A="--full --steps 20 --warmup 5 --no-cpu-baseline --no-parity-leg --b100-steps 0 --config1-steps 0"
 IFS=';' read -ra VS <<< "${VARIANTS:-}"
 for r in $(seq 1 ${REPS:-2}); do
   i=0

@@ -4,7 +4,9 @@ library's TCP transport (RCCL refuses two ranks on one device), and rank 0
 prints one line with n_gpus 2, the world-2 exchange block and — at every N —
 the config-4, LR (config 3) and sent2vec (config 5) legs, each with its own
 exchange accounting.  A rank that dies mid-run ends the command with rc != 0
-within the deadline instead of leaving its sibling waiting in a collective."""
+within the deadline instead of leaving its sibling waiting in a collective.
+Those legs and blocks belong to `--full`; a plain run times the headline's
+steps only and, with `--dump-outputs`, writes what they trained."""
 import json
 import os
 import subprocess
@@ -17,8 +19,10 @@ from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
-SMALL = ["--steps", "2", "--warmup", "1", "--tokens", "1000000", "--vocab", "50000", "--minibatch", "200",
-         "--no-cpu-baseline", "--no-parity-leg", "--b100-steps", "0", "--config1-steps", "0"]
+PLAIN = ["--tokens", "1000000", "--vocab", "50000", "--minibatch", "200"]
+# --full: the exchange block, the roofline and the legs beside the headline are measured only there
+SMALL = ["--full", "--steps", "2", "--warmup", "1"] + PLAIN + [
+    "--no-cpu-baseline", "--no-parity-leg", "--b100-steps", "0", "--config1-steps", "0"]
 LEGS = ["--config4-tokens", "2000000", "--config4-steps", "2", "--lr-batch", "4096", "--app-steps", "3",
         "--s2v-docs", "256"]
 
@@ -100,3 +104,52 @@ def test_bench_gpus1_lr_sharded_base_forms(lib, gpu):
     assert q["value"] > 0 and q["in_place"]["value"] > 0 and "SWPS_PULL_IN_PLACE=0" in q["note"]
     assert "key-sharded PS over 1 GPU(s)" in q["parallelism"]
     assert s2["value"] == s2["config"]["end_to_end"]["value"] and s2["config"]["steady_state"]["value"] > 0
+
+
+def _bench_main(monkeypatch, capsys, argv):
+    """bench.main() in this process (no second interpreter start), its one JSON line parsed."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    monkeypatch.setattr(b, "arm_deadline", lambda rank: None)  # no 1500-s timer left in the test session
+    monkeypatch.setenv("SWPS_BENCH_EXCHANGE", "auto")          # main() sets it: restored afterwards
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    capsys.readouterr()
+    b.main()
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(lib, gpu, tmp_path, monkeypatch, capsys):
+    """Without --full the line carries the headline's fields and nothing measured beside them;
+    --steps sets the timed minibatches (the learner's batch counter = warmup + steps);
+    --dump-outputs writes float32 / float64 arrays, under 64 MB in all, equal bit for bit
+    between two runs with the same arguments and different after one more step."""
+    import numpy as np
+    runs = []
+    for name, steps in (("a", 3), ("b", 3), ("c", 4)):
+        d = tmp_path / name
+        out = _bench_main(monkeypatch, capsys, ["--gpus", "1", "--steps", str(steps), "--warmup", "1"] + PLAIN
+                          + ["--dump-outputs", str(d)])
+        assert out["steps"] == steps and out["warmup"] == 1 and out["n_gpus"] == 1
+        assert out["value"] > 0 and out["ms_per_step"] > 0 and out["unit"] == "words/s"
+        assert out["higher_is_better"] is True and "bfp32" in out["config"]["mode"] and out["dtype"].startswith("f32")
+        for k in ("roofline", "kernel_ms", "other_modes", "minibatch_100", "config1", "exchange"):
+            assert out[k] is None, k
+        assert not {"cpu_baseline", "config4", "lr", "s2v"} & set(out)
+        arrs = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert sorted(arrs) == ["stats", "table_keys", "table_rows"]
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 10 ** 6
+        rows, keys, st = arrs["table_rows"], arrs["table_keys"], arrs["stats"]
+        assert rows.dtype == np.float32 and rows.shape == (len(keys), 4 * 300) and len(keys) >= 10000
+        assert np.isfinite(rows).all() and rows[:, 2 * 300:].any()  # AdaGrad sums: rows were pushed
+        k64 = keys[:, 0].astype(np.uint64) << np.uint64(32) | keys[:, 1].astype(np.uint64)
+        assert (k64[1:] > k64[:-1]).all()  # distinct keys, ascending
+        assert st[0] == 1 + steps and 0 < st[1] < st[2]  # batches; kept < words
+        runs.append(arrs)
+    a, b, c = runs
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert np.array_equal(a["table_keys"], c["table_keys"]) and not np.array_equal(a["table_rows"], c["table_rows"])
