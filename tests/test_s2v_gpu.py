@@ -182,6 +182,49 @@ def test_s2v_bench_dim_matches_oracle(lib, oracle_mod, gpu, tmp_path, dtype, D):
         assert rel.max() < 1e-5, rel.max()
 
 
+def _s2v_shape(dtype, D):
+    """k_s2v_docs<T, NCH, TAIL> as swps_s2v_create picks it from D — for the test ids."""
+    chunk = 128 if dtype == "f64" else 256  # elements per 64-lane chunk of 16-B slices
+    full, rem = divmod(D, chunk)
+    return (full, "tail") if full >= 1 and 0 < rem <= 64 else ((D + chunk - 1) // chunk, "full")
+
+
+S2V_SWEEP = ([("f32", D) for D in (256, 260, 320, 324, 512, 516, 576, 580, 768, 772, 832, 836, 1024)]
+             + [("f64", D) for D in (128, 130, 192, 194, 256, 258, 320, 322, 384, 386, 448, 450, 512)])
+
+
+@pytest.mark.parametrize("dtype,D", S2V_SWEEP, ids=["%s-D%d-nch%d_%s" % ((t, D) + _s2v_shape(t, D)) for t, D in S2V_SWEEP])
+def test_s2v_every_docs_shape_matches_oracle(lib, oracle_mod, gpu, tmp_path, dtype, D):
+    """Every k_s2v_docs<T, NCH, TAIL> instantiation (NCH 1-4 whole chunks, and 1-3 chunks plus the
+    scalar tail), at the first element and at the full 64 lanes of each tail and at the first
+    element and the last of each new chunk, against the oracle: the small corpus, W = N = 5, two
+    passes, the dump covering the vocab.  The kernel's arithmetic is fp64 in both table types, so
+    the bars do not depend on D: fp64 within 1e-9, fp32 within 1e-5 of the oracle's fp32-storage
+    mode (full array)."""
+    orc, t, s = run_pair(lib, oracle_mod, tmp_path, dtype=dtype, D=D, W=5, N=5, B=20, niters=2, dump_vocab=150)
+    io, vo, _ = orc.docs()
+    ig, vg, _ = s.docs()
+    assert len(io) == len(ig) > 100 and np.array_equal(io, ig)
+    info, so = s.info(), orc.stats()
+    assert info["inserted"] == so["inserted"] == 0  # the dump covers the vocab: no rand() rows
+    assert info["lstate"] == so["rng"] and info["rand_calls"] == so["rand_calls"]
+    assert vg.shape == vo.shape == (len(io), D) and np.isfinite(vg).all()
+    if dtype == "f64":
+        assert np.allclose(vg, vo, rtol=1e-9, atol=1e-12), np.abs(vg - vo).max()
+    else:
+        rel = np.abs(vg - vo) / np.maximum(np.abs(vo), 1e-3)
+        assert rel.max() < 1e-5, rel.max()
+
+
+@pytest.mark.parametrize("dtype,D", [("f32", 1028), ("f64", 514)])
+def test_s2v_dim_past_last_shape_refused(lib, gpu, tmp_path, dtype, D):
+    corpus = int_corpus(str(tmp_path / "c.txt"), 10, 20, seed=1)
+    t = lib.Table("w2v", dim=D, capacity=64, dtype=dtype)
+    s = lib.Sent2Vec(t, window=2, negative=2, minibatch=3, unigram_size=10 ** 5)
+    with pytest.raises(lib.SwpsError, match="SWPS_E_UNSUPPORTED: dim too large"):
+        s.load_text(corpus)  # the context is created on the first load
+
+
 def _tokens_of(lib, path):
     """(tok_keys, line_off, sent_ids) of a text corpus as the loaders parse it: split(" "), atoi
     keys (word2vec.h:206,212-224), sentence id = BKDR of the line (sent2vec.cpp:75)."""

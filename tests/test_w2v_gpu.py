@@ -193,13 +193,17 @@ def test_fast_mode_close_to_parity_mode(lib, oracle_mod, gpu, tmp_path):
 @pytest.mark.parametrize("dtype,fp64i,overlap,D", [("f64", True, True, 16), ("f32", True, True, 16),
                                                   ("f32", False, True, 16), ("f32", False, False, 16),
                                                   ("f32", False, True, 300), ("f32", False, False, 300),
-                                                  ("f32", "bfp40", True, 300), ("f32", "bfp40", True, 100)])
+                                                  ("f32", "bfp40", True, 300), ("f32", "bfp40", True, 100)]
+                         + [("f32", m, True, D) for D in (200, 352, 512) for m in ("bfp40", "bfp32")]
+                         + [("f32", False, True, 576)])
 def test_sharded_world1_equals_unsharded(lib, gpu, tmp_path, dtype, fp64i, overlap, D):
     """The sharded request / serve / step / push path with one rank (gloo,
     world 1) reproduces the single-GPU path bit for bit — in fast mode too,
     where the push payload is fp32, and at D = 300, where the learner's mean
     gradients come from the fused k_push_thp<TO_GRADS> and the single GPU's
-    update from the in-place k_push_thp."""
+    update from the in-place k_push_thp.  D = 200 / 352 / 512: k_push_b<...,
+    TO_GRADS> at the <1,0>, <1,2> and <2,0> lane layouts, both residual widths;
+    D = 576: the two-chunk tail kernels, whose push is not fused."""
     import torch.distributed as dist
     from swiftmpi_amd.dist import ShardedWord2Vec
     path = zipf_corpus(str(tmp_path / "c.txt"), 120, 300, seed=31)
