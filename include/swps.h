@@ -260,6 +260,49 @@ int swps_barrier(swps_table *t);
  * payload bytes sent, payload bytes sent to other ranks, keys served] */
 int swps_route_stats(swps_table *t, uint64_t *out6);
 
+/* ---- top-k nearest-neighbour and analogy queries (swps_nearest.hip) ------
+ * The reference only dumps rows (sparsetable.h:127-132); its users answer `distance` /
+ * `word-analogy` questions on the host from the dump.  These calls score queries against the
+ * HBM-resident shard: one D-block of every row (SWPS_LAYOUT_W2V: part 0 = h, part 1 = v; LR
+ * tables hold scalars and are refused with SWPS_E_CFG), F64 rows converted to fp32, scores in
+ * fp32 as a k-ordered fma chain (the f32-input MFMA):
+ *   SWPS_METRIC_DOT  q.r
+ *   SWPS_METRIC_COS  (q.r) / sqrtf(r.r), 0 for a row with r.r == 0; the query is not normalised,
+ *                    so the ranking is the cosine ranking
+ * and returns, per query, the best k rows under the total order "higher score first; equal
+ * scores: smaller key first; NaN scores last".  A row's score depends only on its values, the
+ * query, D, part and metric, so the answer does not depend on the insertion order, on nq, on k
+ * or on how the keys are sharded, bit for bit.
+ *   d_q      [nq][D] fp32 queries
+ *   k        1..64; when fewer than k rows qualify the tail is key ~0, score -inf
+ *   d_excl   [nq][nexcl] keys never returned for that query (~0: unused slot), nexcl <= 8; or NULL
+ *   d_cand   ncand keys that restrict the search (keys the shard lacks are skipped); NULL: all rows
+ *   outputs  [nq][k] keys and scores
+ * Bad k / part / metric / nexcl -> SWPS_E_CFG.  nq == 0 returns SWPS_OK.  The calls run on the
+ * table's stream and synchronise before they return.  The _h forms take host pointers.
+ * swps_analogy gathers the rows of (a, b, c) = d_abc[q][0..2], forms q = (b - a) + c in fp32 in
+ * that order (operands not normalised), excludes a, b and c and runs swps_nearest; a key of
+ * d_abc that no shard holds -> SWPS_E_BADKEY.
+ * On a routed table (swps_table_route) the four calls are COLLECTIVE: every rank passes the same
+ * arguments, between rounds (no rank inside swps_finish).  Each rank scores its own shard, the
+ * [nq][k] candidates are all-gathered and every rank merges them to the same full answer; the
+ * a / b / c rows are all-gathered as copies of their owner's values.  Results are bit-identical
+ * to an unrouted table holding all rows. */
+#define SWPS_METRIC_DOT 0
+#define SWPS_METRIC_COS 1
+#define SWPS_NEAREST_MAX_K 64
+#define SWPS_NEAREST_MAX_EXCL 8
+int swps_nearest(swps_table *t, int32_t part, int32_t metric, const float *d_q, uint64_t nq, int32_t k,
+                 const uint64_t *d_excl, int32_t nexcl, const uint64_t *d_cand, uint64_t ncand,
+                 uint64_t *d_keys_out, float *d_scores_out);
+int swps_nearest_h(swps_table *t, int32_t part, int32_t metric, const float *q, uint64_t nq, int32_t k,
+                   const uint64_t *excl, int32_t nexcl, const uint64_t *cand, uint64_t ncand, uint64_t *keys_out,
+                   float *scores_out);
+int swps_analogy(swps_table *t, int32_t part, int32_t metric, const uint64_t *d_abc, uint64_t nq, int32_t k,
+                 const uint64_t *d_cand, uint64_t ncand, uint64_t *d_keys_out, float *d_scores_out);
+int swps_analogy_h(swps_table *t, int32_t part, int32_t metric, const uint64_t *abc, uint64_t nq, int32_t k,
+                   const uint64_t *cand, uint64_t ncand, uint64_t *keys_out, float *scores_out);
+
 /* ---- word2vec CBOW negative sampling (apps/word2vec) --------------------- */
 typedef struct swps_w2v swps_w2v;
 

@@ -236,6 +236,86 @@ class Table:
         grads = np.ascontiguousarray(grads, dtype=np.float64 if self.layout == "w2v" else np.float32)
         check(capi.lib().swps_push_h(self.h, ptr(keys), len(keys), ptr(grads)))
 
+    # ---- top-k queries (swps_nearest / swps_analogy; collective on a routed table) ----
+    _PARTS = {"h": 0, "v": 1, 0: 0, 1: 1}
+    _METRICS = {"dot": capi.METRIC_DOT, "cos": capi.METRIC_COS, 0: 0, 1: 1}
+
+    def _query_args(self, part, metric):
+        # integer ids the library does not know pass through: it answers SWPS_E_CFG
+        part, metric = self._PARTS.get(part, part), self._METRICS.get(metric, metric)
+        if not isinstance(part, int) or not isinstance(metric, int):
+            raise ValueError("part is 'h' or 'v', metric 'dot' or 'cos'")
+        return part, metric
+
+    @staticmethod
+    def _keys_like(x, on_device, device):
+        """x as a contiguous key array of the call's kind (None stays None)."""
+        if x is None:
+            return None
+        if on_device:
+            import torch
+            if not hasattr(x, "data_ptr"):
+                x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.uint64).view(np.int64))
+            return x.to(device).contiguous()
+        if hasattr(x, "data_ptr"):
+            x = x.cpu().numpy()
+        x = np.ascontiguousarray(x)
+        return x.view(np.uint64) if x.dtype == np.int64 else x.astype(np.uint64, copy=False)
+
+    def nearest(self, queries, k=10, part="v", metric="cos", exclude=None, candidates=None):
+        """The k best rows per query under "higher score first, equal scores: smaller key first,
+        NaN last" (swps_nearest).  queries: [nq, dim] fp32, a CUDA tensor or a numpy array; the
+        answer (keys [nq, k], scores [nq, k]) is of the same kind (tensor keys are int64 views of
+        the u64 keys).  exclude: [nq, <= 8] keys never returned for that query (~0 = unused);
+        candidates: keys that restrict the search.  Fewer than k qualifying rows: the tail is key
+        ~0, score -inf."""
+        part, metric = self._query_args(part, metric)
+        dev = hasattr(queries, "data_ptr")
+        if dev:
+            import torch
+            q = queries.to(torch.float32).contiguous()
+            nq = q.shape[0] if q.dim() == 2 else q.numel() // self.dim
+            keys = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=q.device)
+            scores = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=q.device)
+            fn = capi.lib().swps_nearest
+        else:
+            q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+            nq = q.shape[0]
+            keys = np.empty((nq, max(k, 0)), dtype=np.uint64)
+            scores = np.empty((nq, max(k, 0)), dtype=np.float32)
+            fn = capi.lib().swps_nearest_h
+        excl = self._keys_like(exclude, dev, q.device if dev else None)
+        cand = self._keys_like(candidates, dev, q.device if dev else None)
+        nexcl = 0
+        if excl is not None:
+            excl = excl.reshape(nq, -1)
+            nexcl = int(excl.shape[1])
+        ncand = 0 if cand is None else int(cand.numel() if dev else cand.size)
+        check(fn(self.h, part, metric, ptr(q), nq, k, ptr(excl), nexcl, ptr(cand), ncand, ptr(keys), ptr(scores)))
+        return keys, scores
+
+    def analogy(self, abc_keys, k=1, part="v", metric="cos", candidates=None):
+        """For each (a, b, c) of abc_keys [nq, 3]: the k rows nearest to (b - a) + c (fp32, operands
+        not normalised), a, b and c excluded (swps_analogy).  A CUDA tensor or a numpy array in,
+        the same kind out; an unknown a / b / c raises SWPS_E_BADKEY."""
+        part, metric = self._query_args(part, metric)
+        dev = hasattr(abc_keys, "data_ptr")
+        abc = self._keys_like(abc_keys, dev, abc_keys.device if dev else None).reshape(-1, 3)
+        nq = int(abc.shape[0])
+        cand = self._keys_like(candidates, dev, abc.device if dev else None)
+        if dev:
+            import torch
+            keys = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=abc.device)
+            scores = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=abc.device)
+            fn = capi.lib().swps_analogy
+        else:
+            keys = np.empty((nq, max(k, 0)), dtype=np.uint64)
+            scores = np.empty((nq, max(k, 0)), dtype=np.float32)
+            fn = capi.lib().swps_analogy_h
+        ncand = 0 if cand is None else int(cand.numel() if dev else cand.size)
+        check(fn(self.h, part, metric, ptr(abc), nq, k, ptr(cand), ncand, ptr(keys), ptr(scores)))
+        return keys, scores
+
 
 KT_NAMES = ["plan", "forward", "sort", "gather", "push", "pull", "records"]
 
@@ -266,6 +346,34 @@ class Word2Vec:
         table._deps.add(self)
         self.table = table
         self.dim = table.dim
+        self.key_mode = "atoi" if key_mode == "atoi" else "bkdr"
+
+    def key_of(self, word):
+        """The table key of a word string under the context's key mode (hash_fn / hash_fn2,
+        word2vec_global.h:205-207, word2vec.h:221); integers are keys already."""
+        if not isinstance(word, (str, bytes)):
+            return int(word)
+        if self.key_mode == "bkdr":
+            return bkdr(word)
+        import re
+        m = re.match(r"\s*([+-]?\d+)", word if isinstance(word, str) else word.decode("utf-8", "replace"))
+        return (int(m.group(1)) if m else 0) & 0xFFFFFFFFFFFFFFFF  # atoi
+
+    def most_similar(self, words_or_keys, topn=10, part="v", metric="cos"):
+        """The topn keys nearest to each word's own vector, the word itself excluded
+        (Table.nearest on the HBM shard).  Words are strings (mapped by key_of) or keys; one word
+        or a list.  Returns keys [n, topn] (uint64) — the library keeps no strings."""
+        one = isinstance(words_or_keys, (str, bytes, int, np.integer))
+        keys = np.array([self.key_of(w) for w in ([words_or_keys] if one else words_or_keys)], dtype=np.uint64)
+        import torch
+        dev = torch.device("cuda", self.table.device)
+        dk = torch.from_numpy(keys.view(np.int64)).to(dev)
+        D = self.dim
+        off = Table._PARTS[part] * D
+        q = self.table.export(dk)[:, off:off + D].to(torch.float32)
+        out, _ = self.table.nearest(q, k=topn, part=part, metric=metric, exclude=dk.reshape(-1, 1))
+        out = out.cpu().numpy().view(np.uint64)
+        return out[0] if one else out
 
     def shard_comm(self, comm, frag_num=1000):
         """Library-driven key-sharded mode (swps_w2v_shard_comm): after load_*,

@@ -21,6 +21,8 @@ KEY_BKDR, KEY_ATOI = 0, 1
 W2V_INIT_REF, W2V_INIT_TABLE = 0, 1
 PUSH_ADAGRAD, PUSH_SGD = 0, 1
 LR_PLAN_STEP, LR_PLAN_LOAD, LR_PLAN_NONE = 0, 1, 2
+METRIC_DOT, METRIC_COS = 0, 1
+NEAREST_MAX_K, NEAREST_MAX_EXCL = 64, 8
 COMM_ID_BYTES = 128
 
 # swps_transport callbacks (host all-gather / all-to-all-v)
@@ -100,6 +102,10 @@ PROTOS = {
     "swps_finish": (ctypes.c_int, [_p]),
     "swps_barrier": (ctypes.c_int, [_p]),
     "swps_route_stats": (ctypes.c_int, [_p, _p]),
+    "swps_nearest": (ctypes.c_int, [_p, _i32, _i32, _p, _u64, _i32, _p, _i32, _p, _u64, _p, _p]),
+    "swps_nearest_h": (ctypes.c_int, [_p, _i32, _i32, _p, _u64, _i32, _p, _i32, _p, _u64, _p, _p]),
+    "swps_analogy": (ctypes.c_int, [_p, _i32, _i32, _p, _u64, _i32, _p, _u64, _p, _p]),
+    "swps_analogy_h": (ctypes.c_int, [_p, _i32, _i32, _p, _u64, _i32, _p, _u64, _p, _p]),
     "swps_push_h": (ctypes.c_int, [_p, _p, _u64, _p]),
     "swps_table_find_h": (ctypes.c_int, [_p, _p, _u64, _p]),
     "swps_assign_h": (ctypes.c_int, [_p, _p, _u64, _p]),

@@ -260,6 +260,10 @@ struct swps_table {
   swps::HostStage stage;  // host staging (host transport)
   uint64_t rstats[6] = {0, 0, 0, 0, 0, 0};
   bool finished = false;
+  // swps_nearest / swps_analogy (swps_nearest.hip), grow-only: per-block candidates of a query
+  // batch, the candidate subset's row indices, the local / gathered [nq][k] answers, the
+  // analogy's a / b / c rows with presence flags, its queries and exclusion lists
+  swps::DevMem nn_cand, nn_idx, nn_part, nn_abc, nn_q, nn_excl;
 };
 
 namespace swps {

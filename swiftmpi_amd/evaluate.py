@@ -6,7 +6,10 @@ learn_instance ascends (apps/word2vec/word2vec_global.h:663-718): for a
 sample of positions, neu1 = sum of the full-window context v rows, then
 log sigmoid(neu1 . h_word) + sum over k seeded unigram^0.75 negatives of
 log sigmoid(-neu1 . h_neg).  Higher is better; used to compare training
-modes (lockstep vs pipelined, fast vs parity) on the same corpus."""
+modes (lockstep vs pipelined, fast vs parity) on the same corpus.
+
+nearest_reference / topk_order: the fp64 reference of the query path
+(Table.nearest, swps_nearest.hip) and its total order."""
 import numpy as np
 
 
@@ -39,6 +42,50 @@ def cbow_objective(rows, dim, vid_lines, counts, window=5, negatives=5, position
         total += _log_sigmoid(-(h[neg] @ neu1)).sum()
         n += 1
     return total / max(n, 1)
+
+
+EMPTY_KEY = np.uint64(0xFFFFFFFFFFFFFFFF)
+
+
+def topk_order(scores, keys, k, exclude=None, candidates=None):
+    """The query path's selection (swps_nearest) on given scores [nq, n] of rows with distinct
+    `keys` [n]: per query the best k under the total order "numbers by higher score, equal scores
+    by smaller key; then NaN scores by smaller key", without the query's `exclude` keys
+    ([nq, m], ~0 = unused) and, with `candidates`, among those keys only.  Returns (keys [nq, k]
+    uint64, scores [nq, k] in the scores' dtype); fewer than k rows: the tail is key ~0, score
+    -inf."""
+    scores = np.asarray(scores)
+    keys = np.asarray(keys, dtype=np.uint64)
+    nq = scores.shape[0]
+    out_k = np.full((nq, k), EMPTY_KEY, dtype=np.uint64)
+    out_s = np.full((nq, k), -np.inf, dtype=scores.dtype)
+    base = np.ones(len(keys), dtype=bool) if candidates is None else \
+        np.isin(keys, np.asarray(candidates, dtype=np.uint64))
+    excl = None if exclude is None else np.asarray(exclude, dtype=np.uint64).reshape(nq, -1)
+    for i in range(nq):
+        ok = base if excl is None else base & ~np.isin(keys, excl[i])
+        idx = np.nonzero(ok)[0]
+        s = scores[i, idx]
+        nan = np.isnan(s)
+        order = np.lexsort((keys[idx], -np.where(nan, 0, s), nan))[:k]
+        out_k[i, :len(order)] = keys[idx][order]
+        out_s[i, :len(order)] = s[order]
+    return out_k, out_s
+
+
+def nearest_reference(rows, keys, queries, k, metric="cos", exclude=None, candidates=None):
+    """fp64 reference of Table.nearest: rows [n, D] (one D-block per key), keys [n] distinct,
+    queries [nq, D].  metric "dot": q.r; "cos": (q.r) / sqrt(r.r), 0 for a zero row (the query is
+    not normalised).  Selection and padding as topk_order.  Returns (keys, fp64 scores)."""
+    r = np.asarray(rows, dtype=np.float64)
+    q = np.asarray(queries, dtype=np.float64).reshape(-1, r.shape[1])
+    s = q @ r.T
+    if metric in ("cos", 1):
+        n2 = (r * r).sum(1)
+        s = np.where(n2 == 0, 0.0, s / np.sqrt(np.where(n2 == 0, 1.0, n2)))
+    elif metric not in ("dot", 0):
+        raise ValueError("metric is 'dot' or 'cos'")
+    return topk_order(s, keys, k, exclude, candidates)
 
 
 def text_vid_lines(path, vocab_keys, bkdr):

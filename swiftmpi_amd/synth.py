@@ -107,3 +107,16 @@ def analogy_accuracy(vecs, index, questions, candidates):
             s[pos[index[w]]] = -np.inf
         ok += int(cand[int(np.argmax(s))] == index[d])
     return ok / max(len(questions), 1)
+
+
+def analogy_accuracy_table(table, questions, candidates, key_of, part="v"):
+    """analogy_accuracy on the HBM-resident table: one Table.analogy call (top-1, cosine,
+    a, b, c excluded, fp32 scores) for all questions.  key_of: word -> table key (e.g.
+    swiftmpi_amd.bkdr, Word2Vec.key_of); candidates: the word strings to search among."""
+    if not len(questions):
+        return 0.0
+    abc = np.array([[key_of(w) for w in q[:3]] for q in questions], dtype=np.uint64)
+    want = np.array([key_of(q[3]) for q in questions], dtype=np.uint64)
+    cand = np.array([key_of(w) for w in candidates], dtype=np.uint64)
+    keys, _ = table.analogy(abc, k=1, part=part, metric="cos", candidates=cand)
+    return float((np.asarray(keys).reshape(-1) == want).mean())
