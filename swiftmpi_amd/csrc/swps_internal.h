@@ -65,6 +65,12 @@ template <typename T> int upload(DevMem &m, const std::vector<T> &v, hipStream_t
   return SWPS_OK;
 }
 
+// blocks of bs threads covering `threads` (at least one: an empty launch is an error)
+inline unsigned nblk(uint64_t threads, unsigned bs = 256) {
+  const uint64_t b = (threads + bs - 1) / bs;
+  return (unsigned)(b ? b : 1);
+}
+
 // host staging buffers of a host-transport exchange
 struct HostStage {
   std::vector<char> send, recv;

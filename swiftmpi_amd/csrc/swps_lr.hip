@@ -2446,8 +2446,6 @@ __global__ void k_lr_keys(const int32_t *__restrict__ K, uint64_t n, const uint6
   if (i < n) out[i] = vkeys[K[i]];
 }
 
-inline unsigned nblk(uint64_t n, unsigned bs = 256) { return (unsigned)std::max<uint64_t>(1, (n + bs - 1) / bs); }
-
 struct LTimer {
   bool on = false;
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;  // k >= 16: timer k - 16, not counted

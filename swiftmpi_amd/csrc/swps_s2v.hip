@@ -355,10 +355,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
   }
 }
 
-inline unsigned nblk(uint64_t threads, unsigned bs = 256) {
-  return (unsigned)std::max<uint64_t>(1, (threads + bs - 1) / bs);
-}
-
 enum { ST_REC = 0, ST_DOC, ST_N };
 
 }  // namespace

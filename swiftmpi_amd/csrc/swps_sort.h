@@ -12,6 +12,8 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
+#include "swps_internal.h"
+
 namespace swps {
 
 using OnesweepCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
@@ -143,6 +145,40 @@ inline hipError_t sort_pairs_tiled(int mode, void *tmp, size_t &bytes, const K *
 template <typename K>
 inline hipError_t sort_keys(void *tmp, size_t &bytes, const K *kin, K *kout, uint64_t n, int bits, hipStream_t s) {
   return rocprim::radix_sort_keys<OnesweepCfg>(tmp, bytes, kin, kout, (size_t)n, 0u, (unsigned)bits, s);
+}
+
+// The same sorts with their temporary storage in a grow-only buffer: the size query, tmp.ensure,
+// then the sort.  run = false stops after the ensure: a sizing pass for the largest n, after
+// which the per-step calls allocate nothing.
+template <typename K, typename V>
+inline int sort_pairs(DevMem &tmp, const K *kin, K *kout, const V *vin, V *vout, uint64_t n, int bits, hipStream_t s,
+                      bool run = true) {
+  size_t b = 0;
+  SWPS_HIP(sort_pairs(nullptr, b, kin, kout, vin, vout, n, bits, s));
+  SWPS_TRY(tmp.ensure(b));
+  if (!run) return SWPS_OK;
+  b = tmp.bytes;
+  SWPS_HIP(sort_pairs(tmp.p, b, kin, kout, vin, vout, n, bits, s));
+  return SWPS_OK;
+}
+template <typename K>
+inline int sort_pairs_iota(DevMem &tmp, const K *kin, K *kout, uint32_t *vout, uint64_t n, int bits, hipStream_t s,
+                           bool run = true) {
+  size_t b = 0;
+  SWPS_HIP(sort_pairs_iota(nullptr, b, kin, kout, vout, n, bits, s));
+  SWPS_TRY(tmp.ensure(b));
+  if (!run) return SWPS_OK;
+  b = tmp.bytes;
+  SWPS_HIP(sort_pairs_iota(tmp.p, b, kin, kout, vout, n, bits, s));
+  return SWPS_OK;
+}
+template <typename K> inline int sort_keys(DevMem &tmp, const K *kin, K *kout, uint64_t n, int bits, hipStream_t s) {
+  size_t b = 0;
+  SWPS_HIP(sort_keys(nullptr, b, kin, kout, n, bits, s));
+  SWPS_TRY(tmp.ensure(b));
+  b = tmp.bytes;
+  SWPS_HIP(sort_keys(tmp.p, b, kin, kout, n, bits, s));
+  return SWPS_OK;
 }
 
 }  // namespace swps

@@ -42,13 +42,19 @@
 // scalar tails (element 256*NCH + 64t + lane).  Inactive lanes load a valid
 // duplicate and never store or dot it.
 //
-// Included by swps_w2v.hip inside its anonymous namespace (uses FwdArgs,
-// GatherArgs, PushArgs, run_recs, item_recs, uniform4, slot_row, xcd_block,
-// kGroup, PHead).
+// Included by swps_w2v_learn.hip at file scope, after that unit's own kernel
+// declarations: the kernels here take its argument structs (FwdArgs,
+// GatherArgs, PushArgs) and use its device helpers (run_recs, item_recs,
+// uniform4, slot_row, xcd_block, ItemRecs, PHead, kGroup), which are private
+// to that unit.  Everything else this header uses it includes; kBfpMaxD,
+// bfp_ld and bfp_shape are in swps_w2v_ctx.h.
 #pragma once
+#include "swps_w2v_ctx.h"
+#include "swps_wave.h"
 
-constexpr int kBfpMaxD = 512;
-inline int bfp_ld(int D, int RB) { return (D + RB * D / 4 + 1 + 31) / 32 * 32; }  // floats per row
+namespace {
+
+using swps::wave_sum_pl;
 
 // gfx950 wave max (the permlane / DPP pattern of swps_wave.h: any pairing will do for a max)
 __device__ __forceinline__ int wave_max_i32(int v) {
@@ -636,3 +642,5 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     ri = rn;
   }
 }
+
+}  // namespace

@@ -222,7 +222,7 @@ def test_variant_bit_identical_at_bench_scale(lib, gpu, monkeypatch, env, fixed,
     * SWPS_SORT_WIDE — the minibatch key indices need 18 bits: they sort in two
       9-bit onesweep passes (swps_sort.h) instead of three 8-bit ones (same
       stable order);
-    * SWPS_FUSED_PUSH — k_push_tg sums the single-chunk (key, kind) runs itself
+    * SWPS_FUSED_PUSH — k_push_thp sums the single-chunk (key, kind) runs itself
       and k_gather_t / k_combine only the multi-chunk ones (hot keys of
       thousands of records: the second level runs), vs every run through a
       partial;

@@ -1,7 +1,8 @@
 """Every lane layout the host can dispatch for the word2vec kernels, against
 the oracle.  The instantiation is picked from the dimension D alone
-(bfp_shape / SWPS_BFP_SHAPES, check_cfg's tail / NCH and learn_batch's
-D < 512 / D < 768 ladders in swps_w2v.hip), so the sweep is over D, one test id
+(bfp_shape in swps_w2v_ctx.h, check_cfg's tail / NCH in swps_w2v_ingest.hip,
+and SWPS_BFP_SHAPES / SWPS_NCH_DISPATCH / SWPS_TAIL_DISPATCH, the D < 512 /
+D < 768 ladder, in swps_w2v_learn.hip), so the sweep is over D, one test id
 per (mode, D) so that a failure names the layout:
 
   bfp40 / bfp32   k_forward_b / k_gather_b / k_push_b <NCH, NT>: <0,1> (D = 4,

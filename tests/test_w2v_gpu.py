@@ -380,8 +380,8 @@ def test_alias_sampler_distribution(lib, gpu, tmp_path):
 
 @pytest.mark.parametrize("combine", ["1", "0"])
 def test_fast_kernel_variants_bit_identical(lib, gpu, monkeypatch, combine):
-    """k_push_t (compact-slice push) == k_push, k_push_tg (single-chunk runs
-    summed inside the push, three variants) == k_gather_t + k_push_t, padded == D-strided neu1/neu1e
+    """k_push_t (compact-slice push) == k_push, k_push_thp (single-chunk runs
+    summed inside the push) == k_gather_t + k_push_t, padded == D-strided neu1/neu1e
     rows, 128-B padded == D-strided worker-cache rows, and negatives from the
     coarse-indexed run-length unigram table == the
     1e8-slot table, bit for bit, at the bench's D = 300 (tail) shape in fast mode --
@@ -396,9 +396,8 @@ def test_fast_kernel_variants_bit_identical(lib, gpu, monkeypatch, combine):
     off = np.arange(0, lines * L + 1, L, dtype=np.uint64)
     keys = np.array([lib.bkdr("w%d" % i) for i in range(V)], dtype=np.uint64)
     outs, negs = [], []
-    variants = (("1", "1", "1", "1", "1", "0"), ("0", "1", "1", "1", "1", "0"), ("1", "0", "1", "1", "1", "0"),
-                ("1", "1", "0", "1", "1", "0"), ("1", "1", "1", "0", "1", "0"), ("1", "1", "1", "1", "0", "0"),
-                ("1", "1", "1", "1", "1", "1"), ("1", "1", "1", "1", "1", "2"), ("1", "1", "1", "1", "1", "3"), ("1", "1", "1", "1", "1", "4"), ("1", "1", "1", "1", "1", "5"),
+    variants = (("1", "1", "1", "1", "1", ""), ("0", "1", "1", "1", "1", ""), ("1", "0", "1", "1", "1", ""),
+                ("1", "1", "0", "1", "1", ""), ("1", "1", "1", "0", "1", ""), ("1", "1", "1", "1", "0", ""),
                 ("1", "1", "1", "1", "1", "sort"), ("1", "1", "1", "1", "1", "split"), ("1", "1", "1", "1", "1", "nosplit"),
                 ("1", "1", "1", "1", "1", "nofull"))
     for push_t, pad, uidx, cpad, fused, tgv in variants:
@@ -408,13 +407,11 @@ def test_fast_kernel_variants_bit_identical(lib, gpu, monkeypatch, combine):
         monkeypatch.setenv("SWPS_SPLIT_PUSH", {"split": "1", "nosplit": "0"}.get(tgv, "-1"))
         # nofull: neu1/neu1e and cache rows stored without their zero pad (partial last lines)
         monkeypatch.setenv("SWPS_FULL_LINES", "0" if tgv == "nofull" else "1")
-        tgv = {"sort": "0", "split": "5", "nosplit": "5", "nofull": "5"}.get(tgv, tgv)
         monkeypatch.setenv("SWPS_PUSH_T", push_t)
         monkeypatch.setenv("SWPS_ROW_PAD", pad)
         monkeypatch.setenv("SWPS_UNI_INDEX", uidx)
         monkeypatch.setenv("SWPS_CACHE_PAD", cpad)
         monkeypatch.setenv("SWPS_FUSED_PUSH", fused)
-        monkeypatch.setenv("SWPS_PUSH_TG", tgv)
         t = lib.Table("w2v", dim=300, capacity=V, dtype="f32", learning_rate=0.7)
         w = lib.Word2Vec(t, window=5, negative=5, minibatch=20, sample=1e-3, unigram_size=10 ** 8,
                          fp64_intermediates=False)
