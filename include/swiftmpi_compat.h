@@ -700,7 +700,8 @@ inline int env_int(const char *a, const char *b, int dflt) {
 
 template <class WorkerT, class ServerT, class KeyT> class Cluster {
  public:
-  /* capacity: keys this rank's shard holds (SWPS_CAPACITY overrides the default) */
+  /* capacity: keys this rank's shard holds (SWPS_CAPACITY overrides the default); with
+   * SWPS_MAX_CAPACITY set it is only the starting size */
   explicit Cluster(uint64_t capacity = 0, int32_t dtype = SWPS_F32) {
     if (!capacity) capacity = (uint64_t)env_int("SWPS_CAPACITY", nullptr, 1 << 22);
     _rank = env_int("RANK", "OMPI_COMM_WORLD_RANK", 0);
@@ -718,6 +719,12 @@ template <class WorkerT, class ServerT, class KeyT> class Cluster {
     c.seed = ServerT::init_seed();
     c.push_rule = ServerT::push_rule();
     swps_check(swps_table_create(&c, &_t));
+    /* SWPS_MAX_CAPACITY (unset or 0: fixed capacity): the ceiling under which the shard grows as
+     * keys arrive, like the reference's dense_hash_map; SWPS_CAPACITY stays the starting size */
+    if (const char *mc = std::getenv("SWPS_MAX_CAPACITY")) {
+      const uint64_t max_keys = std::strtoull(mc, nullptr, 10);
+      if (max_keys) swps_check(swps_table_set_max_capacity(_t, max_keys));
+    }
     global_swps_table() = _t;
     global_swps_cfg() = c;
     global_node() = std::make_pair(_rank + 1, _world);

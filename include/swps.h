@@ -93,7 +93,7 @@ typedef struct {
   int32_t layout;     /* SWPS_LAYOUT_* */
   int32_t dtype;      /* SWPS_F32 / SWPS_F64 */
   int32_t dim;        /* D (W2V) — ignored for LR */
-  uint64_t capacity;  /* max keys held by this shard */
+  uint64_t capacity;  /* max keys held by this shard (the starting size under a ceiling, below) */
   float learning_rate; /* server.initial_learning_rate */
   float fudge;        /* AdaGrad fudge factor (reference: 1e-6f) */
   int32_t init_mode;  /* SWPS_INIT_* */
@@ -105,6 +105,49 @@ int swps_table_create(const swps_table_cfg *cfg, swps_table **out);
 int swps_table_destroy(swps_table *t);
 int swps_table_size(swps_table *t, uint64_t *nkeys);
 int swps_table_sync(swps_table *t);
+/* ---- growing the shard ----
+ * A table is created with cfg.capacity rows and, unless asked otherwise, keeps that capacity: key
+ * number capacity + 1 latches SWPS_E_OOM.  Two ways to enlarge a live table; both keep every key,
+ * every row element bit for bit, every row's index, the SWPS_INIT_FLCG draw state, the snapshot
+ * checksum, the route and the latched error flag, and both MOVE the shard: new key / slot / row
+ * buffers are allocated, the index is rebuilt and the rows are copied before the old buffers are
+ * freed, so the peak footprint of a growth is old + new (a doubling: 3x the old rows).
+ *
+ * swps_table_reserve(t, keys): capacity >= keys from now on (a no-op when it already is).  Works
+ *   on any table, with or without a ceiling, and may exceed the ceiling.  Synchronises the device
+ *   when it moves (as swps_table_sync: async forms may have used caller streams).  Slots that an
+ *   earlier overflow claimed without a row are dropped and the row count is clamped to the old
+ *   capacity: reserve after an SWPS_E_OOM repairs the table, and the keys that failed can be pulled
+ *   again.  keys >= 0xFFFFFFF0 -> SWPS_E_CFG; a failed allocation -> SWPS_E_OOM with the table
+ *   unchanged and usable; a table pinned by an app context (below) -> SWPS_E_STATE.  On a routed
+ *   table the call is local, not collective: shards grow independently.
+ *
+ * swps_table_set_max_capacity(t, max_keys): the ceiling under which inserts grow the table by
+ *   themselves.  0 (the default) = fixed capacity.  A positive value must be >= the current
+ *   capacity and < 0xFFFFFFF0, else SWPS_E_CFG; it may be raised or cleared at any time.
+ *   Under a ceiling every inserting call (swps_pull / _h / _async, swps_assign / _h, swps_load,
+ *   swps_restore, a routed pull's owner side, an app context's full pull) first makes room on the
+ *   host (swps_grow_plan) from an upper bound on the row count: the real count at the table's last
+ *   synchronising call plus the n of every insert call since.  n counts keys that may be present
+ *   already, so
+ *     - a table may grow one step earlier than strictly needed: after a call the capacity is at
+ *       most max(capacity before, 2 x capacity before, rows before + n), clipped to the ceiling;
+ *     - the _async forms synchronise the device whenever bound + n exceeds the capacity (a caller
+ *       who wants no sync calls swps_table_reserve first).
+ *   At the ceiling the insert runs as on a fixed table: SWPS_E_OOM is latched exactly when the
+ *   distinct keys exceed the ceiling.  swps_restore of a file with more rows than the capacity
+ *   reserves instead of failing when the file fits under the ceiling.
+ *
+ * Pinning: a word2vec / LR context pins its table once its init has completed (swps_w2v_init,
+ *   swps_lr_init, swps_w2v_install_init, swps_lr_install, swps_w2v_restore_state) until its
+ *   destroy; a sent2vec context from swps_s2v_create to its destroy.  A pinned table never grows
+ *   by itself (the fixed-capacity contract holds) and swps_table_reserve fails with SWPS_E_STATE.
+ *   So a word2vec / LR table may start small under a ceiling: init grows it to the vocabulary.
+ *
+ * swps_table_capacity: out4 = {capacity, max_capacity, slots, growths so far}. */
+int swps_table_reserve(swps_table *t, uint64_t keys);
+int swps_table_set_max_capacity(swps_table *t, uint64_t max_keys);
+int swps_table_capacity(swps_table *t, uint64_t *out4);
 /* per-key element counts of a full row / a pull value / a push value */
 int swps_table_row_elems(swps_table *t, int32_t *row, int32_t *pull, int32_t *push);
 
@@ -478,6 +521,14 @@ int swps_unigram_starts(const uint64_t *keys, const int32_t *counts, uint64_t V,
                         uint64_t *starts);
 /* glibc rand() after srand(seed), `skip` outputs discarded (Vec::randInit's stream) */
 int swps_glibc_rand(uint32_t seed, uint64_t skip, uint64_t n, int32_t *out);
+/* the growth policy of a table under a ceiling, applied before an insert of `incoming` keys into
+ * a table holding nrows of capacity rows:
+ *   new_capacity = capacity when nrows + incoming <= capacity or max_capacity == 0, else
+ *                  min(max(2 capacity, nrows + incoming), max(max_capacity, capacity));
+ *   new_slots    = the smallest power of two >= 2 new_capacity (swps_table_create's rule).
+ * capacity 0 or a capacity / ceiling >= 0xFFFFFFF0 -> SWPS_E_CFG. */
+int swps_grow_plan(uint64_t capacity, uint64_t max_capacity, uint64_t nrows, uint64_t incoming,
+                   uint64_t *new_capacity, uint64_t *new_slots);
 
 /* ---- sent2vec (apps/sent2vec/sent2vec.cpp on apps/word2vec/word2vec.h) ---
  * Sentence vectors against frozen word vectors: Sent2Vec::train

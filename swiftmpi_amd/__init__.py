@@ -24,7 +24,7 @@ from . import capi
 from .capi import SwpsError, check, ptr
 
 __all__ = ["Table", "Word2Vec", "Sent2Vec", "LR", "Config", "SwpsError", "bkdr", "fmix64", "hashfrag_table",
-           "to_node_id", "load_library"]
+           "to_node_id", "load_library", "grow_plan"]
 
 
 def load_library():
@@ -68,6 +68,14 @@ def glibc_rand(n, seed=1, skip=0):
     out = np.zeros(n, dtype=np.int32)
     check(capi.lib().swps_glibc_rand(seed, skip, n, ptr(out)))
     return out
+
+
+def grow_plan(capacity, max_capacity, nrows, incoming):
+    """The growth policy of a table under a ceiling (swps_grow_plan, host only):
+    -> (new_capacity, new_slots) before an insert of `incoming` keys."""
+    nc, ns = ctypes.c_uint64(), ctypes.c_uint64()
+    check(capi.lib().swps_grow_plan(capacity, max_capacity, nrows, incoming, ctypes.byref(nc), ctypes.byref(ns)))
+    return nc.value, ns.value
 
 
 class Config:
@@ -121,7 +129,9 @@ class Table:
     """One HBM parameter shard (SparseTable + server access methods)."""
 
     def __init__(self, layout="w2v", dim=100, capacity=1 << 20, dtype="f32", learning_rate=0.7, fudge=1e-6,
-                 init="hash", seed=0, device=0, push_rule="adagrad"):
+                 init="hash", seed=0, device=0, push_rule="adagrad", max_capacity=None):
+        """max_capacity: the ceiling under which inserts grow the shard by themselves (None / 0:
+        the capacity is fixed, as in the reference-sized default); `capacity` is the starting size."""
         inits = {"hash": capi.INIT_HASH, "zero": capi.INIT_ZERO, "flcg": capi.INIT_FLCG}
         rules = {"adagrad": capi.PUSH_ADAGRAD, "sgd": capi.PUSH_SGD}
         layouts = {"w2v": capi.LAYOUT_W2V, "lr": capi.LAYOUT_LR}
@@ -140,6 +150,8 @@ class Table:
         capi.lib().swps_table_row_elems(self.h, ctypes.byref(r), ctypes.byref(p), ctypes.byref(q))
         self.row_elems, self.pull_elems, self.push_elems = r.value, p.value, q.value
         self._deps = weakref.WeakSet()  # app contexts bound to this shard: closed first
+        if max_capacity:
+            self.set_max_capacity(max_capacity)
 
     def close(self):
         if getattr(self, "h", None):
@@ -163,6 +175,22 @@ class Table:
         n = ctypes.c_uint64()
         check(capi.lib().swps_table_size(self.h, ctypes.byref(n)))
         return n.value
+
+    # ---- growth (swps_table_reserve / _set_max_capacity / _capacity) ----
+    def reserve(self, keys):
+        """Capacity >= keys from now on: moves the shard (every key, row and row index kept; peak
+        footprint old + new) unless it already has the room.  SWPS_E_STATE while an app context
+        that completed its init holds the table."""
+        check(capi.lib().swps_table_reserve(self.h, keys))
+
+    def set_max_capacity(self, max_keys):
+        """The ceiling of automatic growth (0: fixed capacity)."""
+        check(capi.lib().swps_table_set_max_capacity(self.h, max_keys))
+
+    def capacity(self):
+        out = np.zeros(4, dtype=np.uint64)
+        check(capi.lib().swps_table_capacity(self.h, ptr(out)))
+        return dict(zip(["capacity", "max_capacity", "slots", "growths"], (int(x) for x in out)))
 
     def pull(self, keys):
         """keys: int64/uint64 CUDA tensor of distinct keys -> [n, pull_elems] tensor."""

@@ -78,6 +78,10 @@ PROTOS = {
     "swps_table_destroy": (ctypes.c_int, [_p]),
     "swps_table_size": (ctypes.c_int, [_p, ctypes.POINTER(_u64)]),
     "swps_table_sync": (ctypes.c_int, [_p]),
+    "swps_table_reserve": (ctypes.c_int, [_p, _u64]),
+    "swps_table_set_max_capacity": (ctypes.c_int, [_p, _u64]),
+    "swps_table_capacity": (ctypes.c_int, [_p, _p]),
+    "swps_grow_plan": (ctypes.c_int, [_u64, _u64, _u64, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "swps_table_row_elems": (ctypes.c_int, [_p, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "swps_pull": (ctypes.c_int, [_p, _p, _u64, _p]),
     "swps_push": (ctypes.c_int, [_p, _p, _u64, _p]),

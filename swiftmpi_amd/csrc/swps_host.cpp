@@ -3,6 +3,7 @@
 #include <fcntl.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <fstream>
 
@@ -256,6 +257,25 @@ int swps_hashfrag_table(int32_t frag_num, int32_t num_nodes, uint32_t *out) {
 int swps_to_node_id(const uint64_t *keys, uint64_t n, int32_t frag_num, const uint32_t *table, int32_t *out) {
   if (frag_num <= 0) return swps::fail(SWPS_E_CFG, "frag_num must be positive");
   for (uint64_t i = 0; i < n; i++) out[i] = (int32_t)table[swps::fmix64(keys[i]) % (uint64_t)frag_num];
+  return SWPS_OK;
+}
+
+// The growth policy of a table under a ceiling (swps_table_set_max_capacity), as the insert sites
+// apply it before their kernel launches: room for nrows + incoming keys at the least, a doubling
+// at the least, never past the ceiling; a table without one never grows.
+int swps_grow_plan(uint64_t capacity, uint64_t max_capacity, uint64_t nrows, uint64_t incoming,
+                   uint64_t *new_capacity, uint64_t *new_slots) {
+  if (!new_capacity || !new_slots) return swps::fail(SWPS_E_CFG, "null argument");
+  if (capacity == 0 || capacity >= 0xFFFFFFF0ULL || max_capacity >= 0xFFFFFFF0ULL)
+    return swps::fail(SWPS_E_CFG, "capacity out of range");
+  const uint64_t need = incoming > ~0ULL - nrows ? ~0ULL : nrows + incoming;
+  uint64_t nc = capacity;
+  if (need > capacity && max_capacity != 0)
+    nc = std::min(std::max(2 * capacity, need), std::max(max_capacity, capacity));
+  uint64_t ns = 1;
+  while (ns < 2 * nc) ns <<= 1;  // swps_table_create's rule
+  *new_capacity = nc;
+  *new_slots = ns;
   return SWPS_OK;
 }
 

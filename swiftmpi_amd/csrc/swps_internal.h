@@ -56,6 +56,24 @@ struct DevMem {
     bytes = nb;
     return SWPS_OK;
   }
+  // exactly b bytes into an EMPTY buffer (no headroom): the table's four buffers when the shard
+  // grows, where 1/8 of the rows is gigabytes; the old buffer is not touched — the caller fills
+  // the new one and swap()s the two once nothing can fail any more
+  int alloc_exact(size_t b) {
+    if (p) return fail(SWPS_E_STATE, "alloc_exact on a buffer in use");
+    const size_t nb = b ? b : 16;
+    if (hipMalloc(&p, nb) != hipSuccess) {
+      (void)hipGetLastError();
+      p = nullptr;
+      return fail(SWPS_E_OOM, "hipMalloc of " + std::to_string(nb) + " bytes failed");
+    }
+    bytes = nb;
+    return SWPS_OK;
+  }
+  void swap(DevMem &o) {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+  }
   template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
@@ -250,6 +268,14 @@ struct swps_table {
   swps::DevMem counters;  // [0] = nrows (u32), [1] = error flag
   swps::DevMem scratch;   // per-call row indices
   uint32_t host_nrows = 0;
+  // growth (swps_table_set_max_capacity / swps_table_reserve)
+  uint64_t max_capacity = 0;  // ceiling of automatic growth (0: fixed capacity)
+  uint64_t rows_bound = 0;    // host upper bound on the row count: the real count at the last check
+                              // plus the n of every insert call since (growable tables only)
+  hipStream_t ins_stream = nullptr;  // the stream of those insert calls ...
+  bool ins_pending = false, ins_mixed = false;  // ... any since the last check / more than one stream
+  uint64_t growths = 0;
+  int pins = 0;  // app contexts that read rows / row indices of this table: no growth while > 0
   swps::DevMem push_scratch, sort_tmp;  // table_push_sources: (row, position) pairs and their sort
   bool distinct_push = true;  // table_push_sources: one source skips the grouping sort (SWPS_PUSH_DISTINCT=0: off)
   bool slice_push = true;  // table_push_sources: k_push_w2v_multi_t for fp32 D = 256k + t (SWPS_SLICE_PUSH=0: off)
@@ -285,6 +311,15 @@ int table_find_or_insert_placed(swps_table *t, const uint64_t *d_keys, uint64_t 
 int table_lookup(swps_table *t, const uint64_t *d_keys, uint64_t n, uint32_t *d_rows_out, hipStream_t s);
 int table_probe(swps_table *t, const uint64_t *d_keys, uint64_t n, uint32_t *d_rows_out, hipStream_t s);
 int table_check_error(swps_table *t, hipStream_t s);
+// an app context whose init completed holds row indices and reads t->rows at every launch: while
+// any context pins the table it neither grows by itself nor may be reserved
+void table_pin(swps_table *t);
+void table_unpin(swps_table *t);
+inline void table_pin_once(swps_table *t, bool &held) {  // held: the context's own flag
+  if (held) return;
+  table_pin(t);
+  held = true;
+}
 int table_set_rows(swps_table *t, const uint32_t *d_rows, uint64_t n, const void *d_vals, hipStream_t s);
 int table_get_rows(swps_table *t, const uint32_t *d_rows, uint64_t n, void *d_vals, hipStream_t s);
 int table_copy_pull(swps_table *t, const uint32_t *d_rows, uint64_t n, void *d_vals, hipStream_t s);

@@ -2519,6 +2519,7 @@ struct swps_lr {
   // per tile), and the octile order measured 24.7 -> 25.3 us (A/B, round 4)
   int xcd = 0;
   bool loaded = false, inited = false;
+  bool pinned = false;  // table_pin held (from the completed init to destroy)
   uint64_t cursor = 0, nbatches = 0;
   DevMem d_label, d_row_off, d_fvid, d_fval, d_vid_row, d_err, d_err2, d_val_s, d_tmp, d_pred, d_longs;
   DevMem d_frow, d_urow;  // single GPU: shard row per record's feature / per run (built at the first batch)
@@ -4208,6 +4209,7 @@ int swps_lr_destroy(swps_lr *l) {
   if (l->ev_rows) (void)hipEventDestroy(l->ev_rows);
   l->timer.resolve();
   if (l->h_small) (void)hipHostFree(l->h_small);
+  if (l->pinned) table_unpin(l->t);
   delete l->drv;
   delete l;
   (void)hipGetLastError();  // leave no sticky error from the calls above
@@ -4325,6 +4327,9 @@ int swps_lr_init(swps_lr *l) {
     }
     SWPS_HIP(hipStreamSynchronize(l->s));
   }
+  // the full pull may have grown the shard: hot codes need every row index below kLrHotBit
+  if (l->t->cfg.capacity > (uint64_t)kLrHotBit) l->hot = 0;
+  table_pin_once(l->t, l->pinned);  // vid_row / slot rows index the shard from here on
   l->inited = true;
   return SWPS_OK;
 }
@@ -4684,6 +4689,8 @@ int swps_lr_install(swps_lr *l, const float *d_vals) {
     k_lr_install<<<nblk(V), 256, 0, l->s>>>(l->d_init_order.as<int32_t>(), V, d_vals, l->d_wcache.as<float>(),
                                             nullptr, 1);
   SWPS_HIP(hipGetLastError());
+  if (l->t->cfg.capacity > (uint64_t)kLrHotBit) l->hot = 0;  // as swps_lr_create, after the full pull's growth
+  table_pin_once(l->t, l->pinned);  // vid_row / slot rows index the shard from here on
   l->inited = true;
   return SWPS_OK;
 }

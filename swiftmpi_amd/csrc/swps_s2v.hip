@@ -1472,6 +1472,9 @@ int swps_s2v_create(swps_table *t, const swps_s2v_cfg *cfg, swps_s2v **out) {
     delete m;
     return rc;
   }
+  // a pass inserts its pull misses through its own pipelined path while training kernels read the
+  // table: no growth under a sent2vec context, from here to destroy
+  table_pin(t);
   *out = m;
   return SWPS_OK;
 }
@@ -1484,6 +1487,7 @@ int swps_s2v_destroy(swps_s2v *m) {
   if (m->ev_rec) (void)hipEventDestroy(m->ev_rec);
   for (auto e : m->ev_docs)
     if (e) (void)hipEventDestroy(e);
+  table_unpin(m->t);
   delete m;
   (void)hipGetLastError();  // leave no sticky error from the calls above
   return SWPS_OK;

@@ -78,6 +78,31 @@ __global__ void k_find_or_insert(const uint64_t *__restrict__ keys, uint64_t n, 
   if (out_new) out_new[i] = isnew;
 }
 
+// The index of a grown shard (table_move): row r < nrows claims a slot of the NEW slot array for
+// row_key[r], probing from its hash under the new mask with k_find_or_insert's CAS, and stores its
+// own index there.  The keys are distinct (they are the old table's), so no thread meets its own
+// key or waits for another: a lost CAS only moves on to the next slot.  nrows <= new capacity <=
+// nslots / 2, so an empty slot always exists; nothing reads slot_row before the kernel ends.  A
+// latency-bound scatter (one 8-B load, one CAS, one 4-B store per row, all to random lines).
+__global__ __launch_bounds__(256) void k_rehash(const uint64_t *__restrict__ row_key, uint64_t nrows, uint64_t *tkeys,
+                                                uint32_t *__restrict__ slot_row, uint64_t mask) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nrows) return;
+  const uint64_t key = row_key[r];
+  uint64_t s = slot_hash(key) & mask;
+  for (uint64_t probe = 0; probe <= mask; probe++) {
+    if (__hip_atomic_load(&tkeys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == kEmptyKey) {
+      const unsigned long long old =
+          atomicCAS((unsigned long long *)&tkeys[s], (unsigned long long)kEmptyKey, (unsigned long long)key);
+      if (old == kEmptyKey) {
+        slot_row[s] = (uint32_t)r;
+        return;
+      }
+    }
+    s = (s + 1) & mask;
+  }
+}
+
 // table_find_or_insert_placed, step 1: a key the table holds gets its row; a new key claims its
 // slot (out = the slot index, isnew = 1) and gets its row from step 2.  The keys of one call are
 // distinct (the caller's contract): a key found claimed but unpublished is an error, never a wait.
@@ -540,11 +565,93 @@ int table_check_error(swps_table *t, hipStream_t s) {
   SWPS_HIP(hipMemcpyAsync(h, t->counters.p, sizeof(h), hipMemcpyDeviceToHost, s));
   SWPS_HIP(hipStreamSynchronize(s));
   t->host_nrows = h[0] > t->cfg.capacity ? (uint32_t)t->cfg.capacity : h[0];
+  // the growth bound follows the real count, unless an async insert may still be in flight on a
+  // stream this call did not wait for (the sum of the calls' n stays an upper bound then)
+  if (!t->ins_pending || (!t->ins_mixed && t->ins_stream == s)) {
+    t->rows_bound = t->host_nrows;
+    t->ins_pending = t->ins_mixed = false;
+  }
   if (h[1]) {
     uint32_t z = 0;
     SWPS_HIP(hipMemcpy((uint32_t *)t->counters.p + 1, &z, 4, hipMemcpyHostToDevice));
     return table_error_code(h[1]);
   }
+  return SWPS_OK;
+}
+
+void table_pin(swps_table *t) { t->pins++; }
+
+void table_unpin(swps_table *t) {
+  if (t->pins > 0) t->pins--;
+  t->rows_bound = t->cfg.capacity;  // not kept while pinned: the next insert reads the real count
+}
+
+// The move: a shard of new_cap >= cfg.capacity rows with every key, row and row
+// index of this one.  New buffers of exactly the new sizes, the index rebuilt by k_rehash from
+// row_key, row_key and rows copied device to device; the table's own buffers are swapped in only
+// after everything has completed, so any failure leaves the table as it was.  Slots an overflow
+// left as kFullRow have no row and are not carried over; the row counter is clamped to the old
+// capacity (which reads the same to every kernel: full).  Peak footprint: old + new.
+static int table_move(swps_table *t, uint64_t new_cap) {
+  SWPS_HIP(hipDeviceSynchronize());  // async calls may have used caller streams
+  uint32_t cnt = 0;
+  SWPS_HIP(hipMemcpy(&cnt, t->counters.p, 4, hipMemcpyDeviceToHost));
+  const uint32_t nrows = cnt > t->cfg.capacity ? (uint32_t)t->cfg.capacity : cnt;
+  uint64_t ns = 1;
+  while (ns < 2 * new_cap) ns <<= 1;
+  const size_t rb = (size_t)t->row_elems * t->esize;
+  DevMem nkeys, nslot, nrkey, nrowsb;
+  SWPS_TRY(nkeys.alloc_exact(ns * 8));
+  SWPS_TRY(nslot.alloc_exact(ns * 4));
+  SWPS_TRY(nrkey.alloc_exact(new_cap * 8));
+  SWPS_TRY(nrowsb.alloc_exact(new_cap * rb));
+  hipStream_t s = t->stream;
+  SWPS_HIP(hipMemsetAsync(nkeys.p, 0xFF, ns * 8, s));
+  SWPS_HIP(hipMemsetAsync(nslot.p, 0xFF, ns * 4, s));
+  if (nrows) {
+    k_rehash<<<blocks_for(nrows), 256, 0, s>>>(t->row_key.as<uint64_t>(), nrows, nkeys.as<uint64_t>(),
+                                                nslot.as<uint32_t>(), ns - 1);
+    SWPS_HIP(hipGetLastError());
+    SWPS_HIP(hipMemcpyAsync(nrkey.p, t->row_key.p, (size_t)nrows * 8, hipMemcpyDeviceToDevice, s));
+    SWPS_HIP(hipMemcpyAsync(nrowsb.p, t->rows.p, (size_t)nrows * rb, hipMemcpyDeviceToDevice, s));
+  }
+  if (cnt != nrows) SWPS_HIP(hipMemcpyAsync(t->counters.p, &nrows, 4, hipMemcpyHostToDevice, s));
+  SWPS_HIP(hipStreamSynchronize(s));
+  t->keys.swap(nkeys);  // the old buffers are freed with the locals
+  t->slot_row.swap(nslot);
+  t->row_key.swap(nrkey);
+  t->rows.swap(nrowsb);
+  t->cfg.capacity = new_cap;
+  t->nslots = ns;
+  t->mask = ns - 1;
+  t->growths++;
+  t->host_nrows = nrows;
+  t->rows_bound = nrows;
+  t->ins_pending = t->ins_mixed = false;
+  return SWPS_OK;
+}
+
+// Before an insert of n keys on stream s: a table under a ceiling (and not pinned) grows on the
+// host side, so the insert kernel never overflows while there is room under the ceiling.  n bounds
+// the new keys from above (some may be present), hence the bound; only when bound + n passes the
+// capacity is the device synchronised for the real count.
+static int ensure_room(swps_table *t, uint64_t n, hipStream_t s) {
+  if (!t->max_capacity || t->pins) return SWPS_OK;
+  if (t->rows_bound > t->cfg.capacity || n > t->cfg.capacity - t->rows_bound) {
+    SWPS_HIP(hipDeviceSynchronize());
+    uint32_t cnt = 0;
+    SWPS_HIP(hipMemcpy(&cnt, t->counters.p, 4, hipMemcpyDeviceToHost));
+    const uint64_t real = std::min<uint64_t>(cnt, t->cfg.capacity);
+    uint64_t nc = 0, ns = 0;
+    SWPS_TRY(swps_grow_plan(t->cfg.capacity, t->max_capacity, real, n, &nc, &ns));
+    if (nc > t->cfg.capacity) SWPS_TRY(table_move(t, nc));
+    t->rows_bound = real;
+    t->ins_pending = t->ins_mixed = false;
+  }
+  t->rows_bound += n;
+  if (t->ins_pending && t->ins_stream != s) t->ins_mixed = true;
+  t->ins_stream = s;
+  t->ins_pending = true;
   return SWPS_OK;
 }
 
@@ -583,6 +690,7 @@ static int init_new_rows(swps_table *t, const uint64_t *d_keys, uint64_t n, cons
 static int find_or_insert_async(swps_table *t, const uint64_t *d_keys, uint64_t n, uint32_t *d_rows_out,
                                 hipStream_t s, bool init = true) {
   if (n == 0) return SWPS_OK;
+  SWPS_TRY(ensure_room(t, n, s));
   SWPS_TRY(t->isnew.ensure(n));
   uint8_t *isnew = t->isnew.as<uint8_t>();
   k_find_or_insert<<<blocks_for(n), 256, 0, s>>>(d_keys, n, t->keys.as<uint64_t>(), t->slot_row.as<uint32_t>(),
@@ -606,6 +714,9 @@ int table_find_or_insert(swps_table *t, const uint64_t *d_keys, uint64_t n, uint
 int table_find_or_insert_placed(swps_table *t, const uint64_t *d_keys, uint64_t n, const uint32_t *place,
                                 uint32_t *d_rows_out, hipStream_t s) {
   if (n == 0) return SWPS_OK;
+  if (t->mask >= 0xFFFFFFFFull) return table_find_or_insert(t, d_keys, n, d_rows_out, s);
+  SWPS_TRY(ensure_room(t, n, s));
+  // grown past 32-bit slot indices just now: n enters the bound twice, which keeps it an upper bound
   if (t->mask >= 0xFFFFFFFFull) return table_find_or_insert(t, d_keys, n, d_rows_out, s);
   // the placement must be a permutation: checked before any slot is claimed, so a bad one leaves
   // the table untouched
@@ -936,7 +1047,38 @@ int swps_table_destroy(swps_table *t) {
 int swps_table_sync(swps_table *t) {
   SWPS_HIP(hipSetDevice(t->cfg.device));
   SWPS_HIP(hipDeviceSynchronize());  // async calls may have used caller streams
+  t->ins_pending = t->ins_mixed = false;  // none is in flight any more
   return table_check_error(t, t->stream);
+}
+
+int swps_table_reserve(swps_table *t, uint64_t keys) {
+  if (!t) return fail(SWPS_E_CFG, "null table");
+  if (keys >= 0xFFFFFFF0ULL) return fail(SWPS_E_CFG, "capacity out of range");
+  if (t->pins)
+    return fail(SWPS_E_STATE, "an app context holds this table's rows (from its init to its destroy): the "
+                              "capacity is fixed meanwhile");
+  if (keys <= t->cfg.capacity) return SWPS_OK;
+  SWPS_HIP(hipSetDevice(t->cfg.device));
+  return table_move(t, keys);
+}
+
+int swps_table_set_max_capacity(swps_table *t, uint64_t max_keys) {
+  if (!t) return fail(SWPS_E_CFG, "null table");
+  if (max_keys != 0 && (max_keys < t->cfg.capacity || max_keys >= 0xFFFFFFF0ULL))
+    return fail(SWPS_E_CFG, "max capacity " + std::to_string(max_keys) + " is below the capacity (" +
+                                std::to_string(t->cfg.capacity) + ") or out of range");
+  t->max_capacity = max_keys;
+  t->rows_bound = t->cfg.capacity;  // not kept on a fixed table: the next insert reads the real count
+  return SWPS_OK;
+}
+
+int swps_table_capacity(swps_table *t, uint64_t *out4) {
+  if (!t || !out4) return fail(SWPS_E_CFG, "null argument");
+  out4[0] = t->cfg.capacity;
+  out4[1] = t->max_capacity;
+  out4[2] = t->nslots;
+  out4[3] = t->growths;
+  return SWPS_OK;
 }
 
 int swps_table_size(swps_table *t, uint64_t *n) {
@@ -1270,6 +1412,8 @@ int swps_restore(swps_table *t, const char *path, int32_t frag_num, int32_t worl
     m = k;
   }
   if (!m) return SWPS_OK;
+  if (m > t->cfg.capacity && t->max_capacity && !t->pins && m <= t->max_capacity)
+    SWPS_TRY(swps_table_reserve(t, m));  // a growable table: room for the file (the insert grows it further)
   if (m > t->cfg.capacity)  // keys new to a partly filled table are caught by the insert
     return fail(SWPS_E_OOM, "snapshot holds " + std::to_string(m) + " rows; table capacity is " +
                                 std::to_string(t->cfg.capacity));

@@ -136,6 +136,7 @@ int swps_w2v_destroy(swps_w2v *w) {
   if (w->ev_half) (void)hipEventDestroy(w->ev_half);
   if (w->ev_gat) (void)hipEventDestroy(w->ev_gat);
   if (w->h_small) (void)hipHostFree(w->h_small);
+  if (w->pinned) table_unpin(w->t);
   delete w->drv;
   delete w;
   (void)hipGetLastError();  // leave no sticky error from the calls above
@@ -292,6 +293,7 @@ int swps_w2v_init(swps_w2v *w) {
   } else {
     SWPS_TRY(pull_all(w));
   }
+  table_pin_once(w->t, w->pinned);  // vid_row / slot rows index the shard from here on
   w->inited = true;
   return SWPS_OK;
 }
@@ -577,6 +579,7 @@ int swps_w2v_install_init(swps_w2v *w, const void *d_vals) {
   if (!w->sharded) return fail(SWPS_E_STATE, "not sharded");
   SWPS_HIP(hipSetDevice(w->t->cfg.device));
   SWPS_TRY(install_init(w, d_vals));
+  table_pin_once(w->t, w->pinned);  // vid_row / slot rows index the shard from here on
   w->inited = true;
   return SWPS_OK;
 }
@@ -858,6 +861,7 @@ int swps_w2v_restore_state(swps_w2v *w, const char *path) {
     w->drv->cursor = w->cursor / nb * w->drv->spe;
     if (w->drv->ops.set_serve_stream) SWPS_TRY(w->drv->ops.set_serve_stream(w, w->drv->S));
   }
+  table_pin_once(w->t, w->pinned);  // vid_row / slot rows index the shard from here on
   w->inited = true;
   return SWPS_OK;
 }

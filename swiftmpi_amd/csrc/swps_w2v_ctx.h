@@ -141,6 +141,7 @@ struct swps_w2v {
   std::vector<int32_t> counts;
   uint64_t train_words = 0;
   bool loaded = false, inited = false;
+  bool pinned = false;  // table_pin held (from the completed init to destroy)
   // schedule (identical every epoch)
   struct Batch {
     uint64_t l0, l1, kofs;
