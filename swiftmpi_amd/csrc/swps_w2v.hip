@@ -102,6 +102,7 @@ int swps_w2v_create(swps_table *t, const swps_w2v_cfg *cfg, swps_w2v **out) {
   if (const char *e = getenv("SWPS_GATHER_GRID")) w->gather_grid = std::max(64, atoi(e));
   if (const char *e = getenv("SWPS_PUSH_WPE")) w->push_wpe = atoi(e);  // A/B: push occupancy
   if (const char *e = getenv("SWPS_PUSH_UNR8")) w->push_unr = atoi(e) ? 8 : 4;  // A/B, tests
+  if (const char *e = getenv("SWPS_ROW_G")) w->row_g = atoi(e) != 0;             // A/B, tests
   int rc = check_cfg(w);
   if (!rc && hipHostMalloc((void **)&w->h_small, 64) != hipSuccess) rc = fail(SWPS_E_OOM, "pinned alloc");
   if (!rc) rc = w->d_rows_touched.ensure(16);

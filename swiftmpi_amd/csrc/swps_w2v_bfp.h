@@ -30,6 +30,9 @@
 //   int32 [0, D)               m = rint(x / (2^(8RB) u)), |m| < 2^31
 //   int8  [0, D) at float D    RB = 1 only: r = rint((x - m 2^(8RB) u) / u)
 //   float D + RB*D/4           u (a power of two, at least the smallest normal)
+//   the next N + 1 floats      neu1 rows only, when the pad holds them (bfp_row_g): g_0..g_N of
+//                              the position, so an h record's g comes in with the row it reads
+//                              anyway instead of by a 4-byte gather from pg
 //   floats up to ld            zero (whole 128-B lines)
 // so x = (m 2^(8RB) + r) u with |error| <= u/2 = 2^-(32+8RB) of 2^e.  Readers
 // sum the m parts in fp64 (exact products) and the r parts in fp32 (2^-31 of
@@ -130,7 +133,7 @@ template <int NCH, int NT, int RB> struct BRow {
   uint32_t r[LaneMap<NCH, NT>::NC];
   int32_t mt[LaneMap<NCH, NT>::NTT];
   int32_t rt[LaneMap<NCH, NT>::NTT];
-  // stl >= 0: this lane's last tail load fetches element stl instead (the row scale; ScaleLane)
+  // stl >= 0: this lane's last tail load fetches float stl instead (the row scale or g; ScaleLane)
   __device__ __forceinline__ void ld(const float *row, const LaneMap<NCH, NT> &mp, int D, int stl = -1) {
     const int8_t *lo = (const int8_t *)(row + D);
 #pragma unroll
@@ -149,24 +152,40 @@ template <int RB> __device__ __forceinline__ float bfp_scale(const float *row, i
 
 // bfp32 rows whose last tail leaves lanes free (D = 300: elements 256..299 on lanes 0..43): the
 // first free lane loads the row scale (float D) with the tail, and the record's scale is a
-// readlane of it — one memory instruction per record less than a separate scale load.
+// readlane of it — one memory instruction per record less than a separate scale load.  The next
+// free lane carries the record's g the same way (float gi of the row: D + 1 + d when g rides in
+// the neu1 row; any valid float otherwise, its value unused).
 template <int NCH, int NT, int RB> struct ScaleLane {
-  int lane = -1;  // wave-uniform: the lane carrying the scale, or -1 (separate load)
-  int stl = -1;   // this lane's tail index override
-  __device__ __forceinline__ ScaleLane(int l, int D) {
+  int lane = -1;   // wave-uniform: the lane carrying the scale, or -1 (separate load)
+  int glane = -1;  // wave-uniform: the lane carrying g, or -1 (separate load)
+  int stl = -1;    // this lane's tail index override when it carries the scale
+  bool isg = false;  // this lane carries g
+  int s0;          // float index of the row scale
+  __device__ __forceinline__ ScaleLane(int l, int D) : s0(D + RB * D / 4) {
     if (RB == 0 && NT > 0) {
       const int f = D - 256 * NCH - 64 * (NT - 1);
       if (f >= 0 && f < 64) {
         lane = f;
         stl = l == f ? D : -1;
+        if (f + 1 < 64) {
+          glane = f + 1;
+          isg = l == f + 1;
+        }
       }
     }
   }
+  // this lane's tail index override for a record whose g is float gi of its row
+  __device__ __forceinline__ int tail(int gi) const { return isg ? gi : stl; }
   // at load time: the separate scale load when no lane carries it (issued with the row's loads)
   __device__ __forceinline__ float ld(const float *row, int D) const { return lane >= 0 ? 0.f : bfp_scale<RB>(row, D); }
+  __device__ __forceinline__ float ldg(const float *row, int gi) const { return glane >= 0 ? 0.f : row[gi]; }
   // at use time (after the loads, so the readlane does not stall the next rows' loads)
   __device__ __forceinline__ float get(const BRow<NCH, NT, RB> &r, float loaded) const {
     if (NT > 0 && lane >= 0) return __int_as_float(__builtin_amdgcn_readlane(r.mt[NT > 0 ? NT - 1 : 0], lane));
+    return loaded;
+  }
+  __device__ __forceinline__ float getg(const BRow<NCH, NT, RB> &r, float loaded) const {
+    if (NT > 0 && glane >= 0) return __int_as_float(__builtin_amdgcn_readlane(r.mt[NT > 0 ? NT - 1 : 0], glane));
     return loaded;
   }
 };
@@ -219,9 +238,11 @@ template <int NCH, int NT> struct DAcc {
     for (int k = 0; k < NT; k++) s += m.ta(k) ? t[k] * (double)r.t[k] : 0.0;
     return s;
   }
-  // the BFP row (layout at the top of this file), whole lines
+  // the BFP row (layout at the top of this file), whole lines; ng > 0 (a neu1 row carrying g): lane
+  // 1 + d holds g_d in gr (d < ng) and the ng floats after the scale take them
   template <int RB>
-  __device__ __forceinline__ void st_bfp(float *row, const LaneMap<NCH, NT> &m, int D, int ld, int lane) const {
+  __device__ __forceinline__ void st_bfp(float *row, const LaneMap<NCH, NT> &m, int D, int ld, int lane,
+                                         float gr = 0.f, int ng = 0) const {
     constexpr int MB = 31 + 8 * RB;  // bits below 2^e kept
     // the largest biased fp64 exponent of this lane's live elements = that of their largest |x|
     double amax = 0.0;
@@ -259,7 +280,8 @@ template <int NCH, int NT> struct DAcc {
         if (RB) lo[m.te[k]] = (int8_t)res(t[k], q);
       }
     const int s0 = D + RB * D / 4;
-    for (int i = s0 + lane; i < ld; i += 64) row[i] = i == s0 ? __int_as_float((e - MB + 127) << 23) : 0.f;
+    for (int i = s0 + lane; i < ld; i += 64)
+      row[i] = i == s0 ? __int_as_float((e - MB + 127) << 23) : i - s0 <= ng ? gr : 0.f;
   }
 };
 
@@ -394,13 +416,34 @@ __global__ __launch_bounds__(256) void k_forward_b(FwdArgs<float, float> a) {
       }
     }
   }
-  acc.template st_bfp<RB>(a.neu1 + (uint64_t)p * a.ld, m, D, a.ld, lane);
+  // g_d from lane d to lane 1 + d, the lane that writes the pad float after the scale's
+  acc.template st_bfp<RB>(a.neu1 + (uint64_t)p * a.ld, m, D, a.ld, lane, __shfl_up(gk, 1, 64), a.rowg);
   ne.template st_bfp<RB>(a.neu1e + (uint64_t)p * a.ld, m, D, a.ld, lane);
-  if (lane <= N) a.pg[(uint64_t)p * (N + 1) + lane] = gk;
+  if (!a.rowg && lane <= N) a.pg[(uint64_t)p * (N + 1) + lane] = gk;  // pg: only when the readers gather it
 }
 
 // record coefficients of a BFP row with scale u (h records: a = g; v records: a = 1)
 template <int RB> __device__ __forceinline__ double coef_m(float a, float u) { return (double)a * (double)u * (RB ? 256.0 : 1.0); }
+
+// One record's row on its way to a gradient sum: the loads (issue) and, after them, its scale and
+// g (use).  gb: the record info's g word (ItemRecs): the gathered g, or with g in the row (rowg)
+// the record's slot d as an integer; h: an h record (neu1 row), else a v record (neu1e row, g = 1).
+template <int NCH, int NT, int RB> struct RecRow {
+  BRow<NCH, NT, RB> v;
+  float sc, g;
+  __device__ __forceinline__ void ld(const float *row, const LaneMap<NCH, NT> &m, const ScaleLane<NCH, NT, RB> &sl,
+                                     int D, bool rowg, bool h, float gb) {
+    const int gi = rowg && h ? sl.s0 + 1 + __float_as_int(gb) : sl.s0;
+    v.ld(row, m, D, sl.tail(gi));
+    sc = sl.ld(row, D);
+    g = rowg ? sl.ldg(row, gi) : gb;
+  }
+  __device__ __forceinline__ void add_to(BAcc<NCH, NT, RB> &acc, const ScaleLane<NCH, NT, RB> &sl, bool rowg,
+                                         bool h) const {
+    const float gg = h ? (rowg ? sl.getg(v, g) : g) : 1.f, u = sl.get(v, sc);
+    acc.axpy(coef_m<RB>(gg, u), gg * u, v);
+  }
+};
 
 // ---- multi-chunk gradient sums (k_gather_t's role under the fused push) ----
 // One wave per chunk of <= 128 records of one (key, kind), software-pipelined
@@ -411,6 +454,7 @@ __global__ __launch_bounds__(256) void k_gather_b(GatherArgs<float> a, double *_
   const int D = a.D;
   const LaneMap<NCH, NT> m(lane, D);
   const ScaleLane<NCH, NT, RB> sl(lane, D);
+  const bool rowg = a.pg == nullptr;  // g rides in the neu1 rows (run_recs left the records' slots d)
   const uint32_t NI = min(a.multi[0], a.max_items);
   const uint32_t stride = gridDim.x * 4;
   uint32_t qi = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -430,27 +474,20 @@ __global__ __launch_bounds__(256) void k_gather_b(GatherArgs<float> a, double *_
     acc.zero();
     ItemRecs rn;
     for (uint32_t r0 = 0; r0 < n; r0 += UNR) {
-      BRow<NCH, NT, RB> rv[UNR];
-      float gg[UNR], sc[UNR];
+      RecRow<NCH, NT, RB> rv[UNR];
 #pragma unroll
       for (int q = 0; q < UNR; q++) {
         const uint32_t idx = min(r0 + q, n - 1);
         const uint32_t pr = idx < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)ri.p0, (int)idx)
                                      : (uint32_t)__builtin_amdgcn_readlane((int)ri.p1, (int)(idx - 64));
-        gg[q] = __int_as_float(idx < 64 ? __builtin_amdgcn_readlane(__float_as_int(ri.g0), (int)idx)
-                                        : __builtin_amdgcn_readlane(__float_as_int(ri.g1), (int)(idx - 64)));
-        const float *row = base + (uint64_t)pr * a.ld;
-        rv[q].ld(row, m, D, sl.stl);
-        sc[q] = sl.ld(row, D);
+        const float gb = __int_as_float(idx < 64 ? __builtin_amdgcn_readlane(__float_as_int(ri.g0), (int)idx)
+                                                 : __builtin_amdgcn_readlane(__float_as_int(ri.g1), (int)(idx - 64)));
+        rv[q].ld(base + (uint64_t)pr * a.ld, m, sl, D, rowg, kind == 0, gb);
       }
       if (r0 == 0) rn = item_recs(a, dn, lane);  // next item's record info, behind this item's first rows
 #pragma unroll
-      for (int q = 0; q < UNR; q++) {
-        if (r0 + q < n) {
-          const float g = kind == 0 ? gg[q] : 1.f, u = sl.get(rv[q], sc[q]);
-          acc.axpy(coef_m<RB>(g, u), g * u, rv[q]);
-        }
-      }
+      for (int q = 0; q < UNR; q++)
+        if (r0 + q < n) rv[q].add_to(acc, sl, rowg, kind == 0);
     }
     if (n == 0) rn = item_recs(a, dn, lane);
     st_f64(partial + (uint64_t)item * D, m, acc, 1.0);
@@ -507,6 +544,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
   const int D = a.D;
   const LaneMap<NCH, NT> m(lane, D);
   const ScaleLane<NCH, NT, RB> sl(lane, D);
+  const bool rowg = a.pg == nullptr;  // g rides in the neu1 rows (run_recs left the records' slots d)
   const uint64_t n2 = 2ull * a.U;
   const uint64_t stride = (uint64_t)gridDim.x * 4;
   uint64_t uh = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -572,30 +610,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     if (cnt && one) {
       const float *base = half == 0 ? a.neu1 : a.neu1e;
       for (uint32_t r0 = 0; r0 < cnt; r0 += UNR) {
-        BRow<NCH, NT, RB> rv[UNR];
-        float gf[UNR], sc[UNR];
+        RecRow<NCH, NT, RB> rv[UNR];
 #pragma unroll
         for (int q = 0; q < UNR; q++) {
           const uint32_t idx = min(r0 + q, cnt - 1);
           const uint32_t pr = idx < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)ri.p0, (int)idx)
                                        : (uint32_t)__builtin_amdgcn_readlane((int)ri.p1, (int)(idx - 64));
-          gf[q] = __int_as_float(idx < 64 ? __builtin_amdgcn_readlane(__float_as_int(ri.g0), (int)idx)
-                                          : __builtin_amdgcn_readlane(__float_as_int(ri.g1), (int)(idx - 64)));
-          const float *prow = base + (uint64_t)pr * a.ld;
-          rv[q].ld(prow, m, D, sl.stl);
-          sc[q] = sl.ld(prow, D);
+          const float gb = __int_as_float(idx < 64 ? __builtin_amdgcn_readlane(__float_as_int(ri.g0), (int)idx)
+                                                   : __builtin_amdgcn_readlane(__float_as_int(ri.g1), (int)(idx - 64)));
+          rv[q].ld(base + (uint64_t)pr * a.ld, m, sl, D, rowg, half == 0, gb);
         }
         if (r0 == 0) {  // the next item's record info, behind this item's first rows
           if (more) rn = recs_of(hn, nx);
           rn_done = true;
         }
 #pragma unroll
-        for (int q = 0; q < UNR; q++) {
-          if (r0 + q < cnt) {
-            const float g = half == 0 ? gf[q] : 1.f, u = sl.get(rv[q], sc[q]);
-            acc.axpy(coef_m<RB>(g, u), g * u, rv[q]);
-          }
-        }
+        for (int q = 0; q < UNR; q++)
+          if (r0 + q < cnt) rv[q].add_to(acc, sl, rowg, half == 0);
       }
     } else if (cnt) {
       if (more) rn = recs_of(hn, nx);

@@ -27,6 +27,9 @@ inline int bfp_shape(int D) {
   if (rem <= 128) return 10 * nch + (rem + 63) / 64;
   return 10 * (nch + 1);
 }
+// g_0..g_N of a position ride in its neu1 row, in the N + 1 floats after the row scale, when the
+// row's zero pad holds them (bfp_ld unchanged): N + 1 then, else 0 (the readers gather pg)
+inline int bfp_row_g(int D, int RB, int N) { return D + RB * D / 4 + 1 + N + 1 <= bfp_ld(D, RB) ? N + 1 : 0; }
 
 // ---- per-kernel HIP-event timing ----------------------------------------
 enum { KT_KEEP = 0, KT_FWD, KT_SORT, KT_GATHER, KT_PUSH, KT_PULL, KT_REC, KT_N };
@@ -115,6 +118,9 @@ struct swps_w2v {
   int push_t = 1;     // fast mode: k_push_t (SWPS_PUSH_T=0: k_push, for A/B timing)
   int push_wpe = 0;  // SWPS_PUSH_WPE: 0 = by batch size, 4 / 1 = k_push_b<1,1,0> at 4 waves per SIMD or not
   int push_unr = 4;  // k_push_b<1,1,0>'s record rows in flight: 4 (SWPS_PUSH_UNR8=1: 8, the previous default)
+  // BFP modes: g rides in the neu1 row where its pad holds it: -1 = batches of at least 65536 keys,
+  // 0 = never (the pg gather), 1 = at any size (SWPS_ROW_G; A/B, tests)
+  int row_g = -1;
   uint32_t gather_grid = 65536;  // k_gather_t / k_combine grid cap in blocks (SWPS_GATHER_GRID; A/B: 2048..65536 -> 65536 best)
   bool cache_pad = true;  // worker-cache rows padded to 128 B (SWPS_CACHE_PAD=0: D-strided, for A/B timing)
   int cs = 0;              // worker-cache row stride in elements (set with the cache allocation)

@@ -107,6 +107,7 @@ template <typename T, typename A> struct FwdArgs {
   int ld;   // neu1/neu1e row stride in elements (D rounded up to 128 B: whole cache lines per row)
   int cs;   // worker-cache row stride in elements (the same rounding)
   int full;  // k_forward_t: neu1/neu1e stores cover the row pad (zeros): whole lines (SWPS_FULL_LINES)
+  int rowg;  // k_forward_b: N + 1 = g goes into the neu1 row's pad and pg is not written; 0 = pg (bfp_row_g)
 };
 
 // Source row of a forward slot: a record entry tagged kTabRow is a row index
@@ -595,6 +596,8 @@ __device__ __forceinline__ uint4 uniform4(uint4 d) {  // wave-uniform value: kee
                     __builtin_amdgcn_readfirstlane(d.z), __builtin_amdgcn_readfirstlane(d.w));
 }
 
+// pg == nullptr: g rides in the neu1 rows (swps_w2v_bfp.h) and an h record's g word is its slot
+// d = index % SH, as an integer
 __device__ __forceinline__ ItemRecs run_recs(const uint32_t *vals, const float *pg, uint32_t SH, uint32_t SV,
                                              uint64_t HOFF, uint32_t s, uint32_t n, uint32_t kind, int lane) {
   ItemRecs r{0, 0, 1.f, 1.f};
@@ -603,7 +606,7 @@ __device__ __forceinline__ ItemRecs run_recs(const uint32_t *vals, const float *
     const uint32_t pi = vals[s + lane];
     if (kind == 0) {
       r.p0 = pi / SH;
-      r.g0 = pg[pi];
+      r.g0 = pg ? pg[pi] : __int_as_float((int)(pi % SH));
     } else {
       r.p0 = (uint32_t)(pi - HOFF) / SV;
     }
@@ -612,7 +615,7 @@ __device__ __forceinline__ ItemRecs run_recs(const uint32_t *vals, const float *
     const uint32_t pi = vals[s + 64 + lane];
     if (kind == 0) {
       r.p1 = pi / SH;
-      r.g1 = pg[pi];
+      r.g1 = pg ? pg[pi] : __int_as_float((int)(pi % SH));
     } else {
       r.p1 = (uint32_t)(pi - HOFF) / SV;
     }
@@ -1258,6 +1261,13 @@ template <typename T, typename A> Rows rows_of(const swps_w2v *w) {
 template <typename A> int inter_ld(const swps_w2v *w) {
   return w->bfp ? bfp_ld(w->D, w->bfp_rb) : row_ld(w->D, sizeof(A), w->row_pad);
 }
+// N + 1 when the step's g rides in the neu1 rows (BFP modes, where the row pad holds it), else 0: the
+// forward, the gather and the push all read it — pg is then neither written nor read.  By default
+// from 65536 keys per batch: below, pg stays in L2 and its gather is the faster of the two (same
+// box, B = 100 lines, per launch: gather 33.0 -> 39.3 us, push 165.6 -> 172.6 us with g in the row)
+inline int row_g(const swps_w2v *w, uint32_t U) {
+  return w->bfp && (w->row_g > 0 || (w->row_g < 0 && U >= 65536)) ? bfp_row_g(w->D, w->bfp_rb, w->N) : 0;
+}
 // at most max_items / kGroup leaders, 4 per block
 inline bool use_combine(const swps_w2v *w, uint64_t M) {
   return w->combine == 1 || (w->combine == 2 && M >= w->combine_min);
@@ -1326,7 +1336,7 @@ template <typename T, typename A> int forward(swps_w2v *w, const swps_w2v::Prepp
   SWPS_TRY(w->d_pg.ensure(pb.HOFF * 4));
   FwdArgs<T, A> fa{w->d_rec.as<int32_t>(), (int)P, w->d_cache_h.as<T>(), w->d_cache_v.as<T>(), w->t->rows.as<T>(),
                    w->d_exptab.as<float>(), D, w->W, w->N, w->cfg.alpha, w->d_neu1.as<A>(), w->d_neu1e.as<A>(),
-                   w->d_pg.as<float>(), w->xcd_order, ld, w->cs, w->full_lines};
+                   w->d_pg.as<float>(), w->xcd_order, ld, w->cs, w->full_lines, row_g(w, pb.U)};
   const unsigned grid = nblk(P * 64);
   const Rows rows = rows_of<T, A>(w);
   hipEvent_t ef = w->timer.begin(s);
@@ -1364,8 +1374,8 @@ int gradient_sums(swps_w2v *w, const swps_w2v::Prepped &pb, const SumPlan &pl, h
   const bool fused = pl.fused();
   SWPS_TRY(w->d_partial.ensure(pb.max_items * D * (w->bfp ? 8 : sizeof(A))));
   GatherArgs<A> ga{w->d_desc.as<uint4>(), w->d_ioff.as<uint32_t>(), w->d_pvals_s.as<uint32_t>(), pb.U,
-                   w->d_neu1.as<A>(), w->d_neu1e.as<A>(), w->d_pg.as<float>(), pb.HOFF, (uint32_t)pb.P, D,
-                   w->d_partial.as<A>(), inter_ld<A>(w), w->d_lead.as<uint32_t>(),
+                   w->d_neu1.as<A>(), w->d_neu1e.as<A>(), row_g(w, pb.U) ? nullptr : w->d_pg.as<float>(), pb.HOFF,
+                   (uint32_t)pb.P, D, w->d_partial.as<A>(), inter_ld<A>(w), w->d_lead.as<uint32_t>(),
                    (uint32_t)pb.max_items, fused ? w->d_multi.as<uint32_t>() : nullptr, (uint32_t)(w->N + 1),
                    (uint32_t)(2 * w->W), !fused && pb.msorted ? w->d_multi.as<uint32_t>() : nullptr};
   // multi-chunk items: at most M / chm full chunks plus one partial chunk per run of > kChunk records
@@ -1459,8 +1469,8 @@ int push(swps_w2v *w, const swps_w2v::Prepped &pb, const SumPlan &pl, const int3
                     w->d_partial.as<A>(), w->t->rows.as<T>(), w->d_local.as<int32_t>(), D,
                     (double)w->t->cfg.learning_rate, (double)w->t->cfg.fudge, d_grads,
                     d_vals ? nullptr : w->d_cache_h.as<T>(), d_vals ? nullptr : w->d_cache_v.as<T>(), w->cs,
-                    w->d_pvals_s.as<uint32_t>(), w->d_pg.as<float>(), w->d_neu1.as<A>(), w->d_neu1e.as<A>(),
-                    pb.HOFF, (uint32_t)pb.P, inter_ld<A>(w), w->d_krow.as<uint32_t>(),
+                    w->d_pvals_s.as<uint32_t>(), row_g(w, pb.U) ? nullptr : w->d_pg.as<float>(), w->d_neu1.as<A>(),
+                    w->d_neu1e.as<A>(), pb.HOFF, (uint32_t)pb.P, inter_ld<A>(w), w->d_krow.as<uint32_t>(),
                     (uint32_t)(w->N + 1), (uint32_t)(2 * w->W), w->full_lines,
                     use_combine(w, pb.M) ? kGroup : 0xFFFFFFFFu};
   // one wave per key for k_push / k_push_t; the (key, half) kernels (k_push_thp, k_push_b) walk a
