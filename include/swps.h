@@ -179,6 +179,68 @@ int swps_assign_h(swps_table *t, const uint64_t *keys, uint64_t n, const double 
  * forms sync once per call there, like swps_pull / swps_push. */
 int swps_pull_async(swps_table *t, const uint64_t *d_keys, uint64_t n, void *d_vals, void *stream);
 int swps_push_async(swps_table *t, const uint64_t *d_keys, uint64_t n, const void *d_grads, void *stream);
+
+/* ---- repeated keys (swps_dup.hip) --------------------------
+ * swps_pull / swps_push take DISTINCT keys.  These calls take a batch of ids as a caller holds
+ * it (a CTR minibatch, token ids): keys may repeat, and the key ~0 (the table's empty key) is a
+ * padding id.  The dedup and the per-key gradient reduction run on the GPU, in a defined order.
+ *
+ * Streams: `stream` is a hipStream_t of the table's device on which the inputs are ready (NULL =
+ * the table's own stream).  The three device calls issue their work there, read the distinct
+ * count on the host once and SYNCHRONISE that stream before they return; they end in the latched
+ * error check, as swps_pull does.  The _h forms take host arrays in the wire types (W2V fp64, LR
+ * fp32) on the table's stream, staged as swps_pull_h stages them.
+ * Limits: n == 0 returns SWPS_OK (a routed table still joins the exchange); n >= 2^32 ->
+ * SWPS_E_UNSUPPORTED (positions are u32); a null table or pointer, a bad insert / gdtype / reduce
+ * -> SWPS_E_CFG, all checked before any device call.
+ *
+ * swps_coalesce: d_uniq[u] = the u-th distinct key in order of FIRST OCCURRENCE, d_inv[i] = the
+ *   index in d_uniq of d_keys[i], d_count[u] = its number of occurrences, *nu = the distinct
+ *   count.  Any output may be NULL.  ~0 is never in d_uniq and its d_inv is 0xFFFFFFFF.  The
+ *   table gives its device and scratch only: no row is read or changed.
+ *
+ * swps_lookup: d_vals[i] = the pull value of d_keys[i] (table dtype).
+ *   insert = 1: every absent distinct key is inserted ONCE, exactly as swps_pull(d_uniq, nu)
+ *     would: same init_param, same growth rule under a ceiling (the insert count is nu, not n:
+ *     afterwards capacity <= max(capacity, 2 x capacity, rows + nu), clipped to the ceiling), same
+ *     SWPS_E_OOM latch; an SWPS_INIT_FLCG table draws in first-occurrence order.  ~0 is the
+ *     SWPS_E_BADKEY it is for swps_pull.  d_found[i] (may be NULL) = 1 wherever a row was returned.
+ *   insert = 0: nothing is inserted, nothing is latched; an absent key or ~0 yields a zero value
+ *     and d_found[i] = 0.
+ *   Works on a pinned table like swps_pull.
+ *
+ * swps_push_dup: for each distinct key with occurrences at positions p1 < p2 < ... < pm
+ *     g = combine(grads[p1], ..., grads[pm])   per element, in fp64 whatever gdtype is
+ *     g *= scale                               one fp64 multiply; 1.0 is the exact identity
+ *     ONE step of the table's push rule with g (W2V: g as fp64; LR: (float)g), the arithmetic
+ *     of swps_push element for element.
+ *   combine: the occurrences, in ascending position, are cut into chunks of SWPS_DUP_CHUNK
+ *   consecutive occurrences; each chunk is a sequential chain starting FROM ITS FIRST ELEMENT (not
+ *   from 0.0); the chunk sums are chained sequentially in chunk order, again from the first;
+ *   SWPS_REDUCE_MEAN divides the sum by (double)m once.  So m <= 128 is the plain left-to-right
+ *   sum, m = 1 passes the gradient through bit for bit, and a call whose keys are distinct with
+ *   scale = 1 leaves the table bit-identical to swps_push.  This order is part of the ABI.
+ *   d_grads is [n][push elems] of gdtype (SWPS_F32 or SWPS_F64; LR tables: SWPS_F32 only).  ~0
+ *   positions are skipped.  A key the table lacks latches SWPS_E_BADKEY as in swps_push; the
+ *   other keys are applied.
+ *
+ * Routed tables: the three calls are COLLECTIVE.  Every rank coalesces its own keys and runs the
+ * routed pull / push on its distinct keys (lookup scatters the values through d_inv; push first
+ * reduces to one gradient per distinct key), so only distinct keys cross the wire and keys shared
+ * between ranks are separate steps in source-rank order, as for swps_push.  insert = 0 is local
+ * only (SWPS_E_UNSUPPORTED on a routed table). */
+#define SWPS_REDUCE_SUM 0
+#define SWPS_REDUCE_MEAN 1
+#define SWPS_DUP_CHUNK 128
+int swps_coalesce(swps_table *t, const uint64_t *d_keys, uint64_t n, uint64_t *d_uniq, uint32_t *d_inv,
+                  uint32_t *d_count, uint64_t *nu, void *stream);
+int swps_lookup(swps_table *t, const uint64_t *d_keys, uint64_t n, int32_t insert, void *d_vals, uint8_t *d_found,
+                void *stream);
+int swps_push_dup(swps_table *t, const uint64_t *d_keys, uint64_t n, const void *d_grads, int32_t gdtype,
+                  int32_t reduce, double scale, void *stream);
+int swps_lookup_h(swps_table *t, const uint64_t *keys, uint64_t n, int32_t insert, void *vals, uint8_t *found);
+int swps_push_dup_h(swps_table *t, const uint64_t *keys, uint64_t n, const void *grads, int32_t reduce,
+                    double scale);
 /* Overwrite / read full rows (table dtype, d_rows[n][row elems]). */
 int swps_assign(swps_table *t, const uint64_t *d_keys, uint64_t n, const void *d_rows);
 int swps_export(swps_table *t, const uint64_t *d_keys, uint64_t n, void *d_rows);

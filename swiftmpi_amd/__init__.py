@@ -264,6 +264,84 @@ class Table:
         grads = np.ascontiguousarray(grads, dtype=np.float64 if self.layout == "w2v" else np.float32)
         check(capi.lib().swps_push_h(self.h, ptr(keys), len(keys), ptr(grads)))
 
+    # ---- repeated keys (swps_coalesce / swps_lookup / swps_push_dup) ----
+    _REDUCE = {"sum": capi.REDUCE_SUM, "mean": capi.REDUCE_MEAN, 0: 0, 1: 1}
+
+    @staticmethod
+    def _stream(x):
+        import torch
+        return ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+
+    def coalesce(self, keys):
+        """keys: an int64 CUDA tensor of any shape; keys may repeat, -1 (~0) is padding.
+        -> (uniq, inv, count): the distinct keys in first-occurrence order, for every position
+        the index of its key in uniq (int64, -1 for padding; shaped like keys) and the number
+        of occurrences of every distinct key (int64).  No row is read or changed."""
+        import torch
+        k = keys.contiguous().view(-1)
+        n = k.numel()
+        uniq = torch.empty(n, dtype=torch.int64, device=k.device)
+        inv = torch.empty(n, dtype=torch.int32, device=k.device)
+        count = torch.empty(n, dtype=torch.int32, device=k.device)
+        nu = ctypes.c_uint64()
+        check(capi.lib().swps_coalesce(self.h, ptr(k), n, ptr(uniq), ptr(inv), ptr(count), ctypes.byref(nu),
+                                       self._stream(k)))
+        return uniq[:nu.value], inv.to(torch.int64).view(keys.shape), count[:nu.value].to(torch.int64)
+
+    def lookup(self, keys, insert=True, return_found=False):
+        """The pull value of every position of `keys` (repeats allowed): an int64 CUDA tensor of any
+        shape -> [*keys.shape, pull_elems] in the table dtype, on torch's current stream; a numpy
+        array -> the host form (wire types: W2V fp64, LR fp32).  insert=True inserts every absent
+        distinct key once, as `pull` of the distinct keys would; insert=False returns zeros for
+        absent keys and padding.  return_found: also the per-position flags (uint8 / bool)."""
+        lib = capi.lib()
+        if hasattr(keys, "data_ptr"):
+            import torch
+            k = keys.contiguous().view(-1)
+            n = k.numel()
+            out = torch.empty((n, self.pull_elems), dtype=self.torch_dtype, device=k.device)
+            found = torch.empty(n, dtype=torch.uint8, device=k.device) if return_found else None
+            check(lib.swps_lookup(self.h, ptr(k), n, int(insert), ptr(out), ptr(found), self._stream(k)))
+            out = out.view(*keys.shape, self.pull_elems)
+            return (out, found.view(keys.shape)) if return_found else out
+        k = self._keys_like(keys, False, None)
+        shape = k.shape
+        k = np.ascontiguousarray(k.reshape(-1))
+        out = np.zeros((len(k), self.pull_elems), dtype=np.float64 if self.layout == "w2v" else np.float32)
+        found = np.zeros(len(k), dtype=np.uint8)
+        check(lib.swps_lookup_h(self.h, ptr(k), len(k), int(insert), ptr(out), ptr(found)))
+        out = out.reshape(*shape, self.pull_elems)
+        return (out, found.reshape(shape)) if return_found else out
+
+    def push_dup(self, keys, grads, reduce="sum", scale=1.0):
+        """One step of the push rule per DISTINCT key of `keys`, with the key's gradients combined
+        in fp64 in ascending position (chunks of 128, each a chain from its first element, the chunk
+        sums chained in order; reduce="mean" divides by the count once), times `scale`.  grads:
+        [*keys.shape, push_elems], fp32 or fp64 (LR tables: fp32), never cast on the host.  CUDA
+        tensors run on torch's current stream; numpy arrays take the host form (wire types).
+        Padding (-1) positions are skipped; a key the table lacks raises SWPS_E_BADKEY after the
+        other keys were applied."""
+        if reduce not in self._REDUCE:
+            raise ValueError("reduce is 'sum' or 'mean'")
+        lib = capi.lib()
+        if hasattr(keys, "data_ptr"):
+            import torch
+            k = keys.contiguous().view(-1)
+            g = grads.contiguous()
+            if g.dtype not in (torch.float32, torch.float64):
+                raise TypeError("grads must be float32 or float64")
+            if g.numel() != k.numel() * self.push_elems:
+                raise ValueError("grads must hold push_elems values per key")
+            gd = capi.F64 if g.dtype == torch.float64 else capi.F32
+            check(lib.swps_push_dup(self.h, ptr(k), k.numel(), ptr(g), gd, self._REDUCE[reduce], float(scale),
+                                    self._stream(k)))
+            return
+        k = np.ascontiguousarray(self._keys_like(keys, False, None).reshape(-1))
+        g = np.ascontiguousarray(grads, dtype=np.float64 if self.layout == "w2v" else np.float32)
+        if g.size != len(k) * self.push_elems:
+            raise ValueError("grads must hold push_elems values per key")
+        check(lib.swps_push_dup_h(self.h, ptr(k), len(k), ptr(g), self._REDUCE[reduce], float(scale)))
+
     # ---- top-k queries (swps_nearest / swps_analogy; collective on a routed table) ----
     _PARTS = {"h": 0, "v": 1, 0: 0, 1: 1}
     _METRICS = {"dot": capi.METRIC_DOT, "cos": capi.METRIC_COS, 0: 0, 1: 1}

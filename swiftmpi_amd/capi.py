@@ -23,6 +23,8 @@ PUSH_ADAGRAD, PUSH_SGD = 0, 1
 LR_PLAN_STEP, LR_PLAN_LOAD, LR_PLAN_NONE = 0, 1, 2
 METRIC_DOT, METRIC_COS = 0, 1
 NEAREST_MAX_K, NEAREST_MAX_EXCL = 64, 8
+REDUCE_SUM, REDUCE_MEAN = 0, 1
+DUP_CHUNK = 128
 COMM_ID_BYTES = 128
 
 # swps_transport callbacks (host all-gather / all-to-all-v)
@@ -88,6 +90,11 @@ PROTOS = {
     "swps_pull_h": (ctypes.c_int, [_p, _p, _u64, _p]),
     "swps_pull_async": (ctypes.c_int, [_p, _p, _u64, _p, _p]),
     "swps_push_async": (ctypes.c_int, [_p, _p, _u64, _p, _p]),
+    "swps_coalesce": (ctypes.c_int, [_p, _p, _u64, _p, _p, _p, ctypes.POINTER(_u64), _p]),
+    "swps_lookup": (ctypes.c_int, [_p, _p, _u64, _i32, _p, _p, _p]),
+    "swps_push_dup": (ctypes.c_int, [_p, _p, _u64, _p, _i32, _i32, ctypes.c_double, _p]),
+    "swps_lookup_h": (ctypes.c_int, [_p, _p, _u64, _i32, _p, _p]),
+    "swps_push_dup_h": (ctypes.c_int, [_p, _p, _u64, _p, _i32, ctypes.c_double]),
     "swps_comm_unique_id": (ctypes.c_int, [_p]),
     "swps_comm_bootstrap_tcp": (ctypes.c_int, [ctypes.c_char_p, _i32, _i32, _i32, _i32, _p]),
     "swps_comm_create_rccl": (ctypes.c_int, [_p, _i32, _i32, _i32, ctypes.POINTER(_p)]),

@@ -254,6 +254,10 @@ struct Config {
 
 }  // namespace swps
 
+namespace swps {
+constexpr int kDupBufs = 16;  // swps_table::dup
+}
+
 // ---- the HBM parameter shard -------------------------------------------------
 struct swps_table {
   swps_table_cfg cfg{};
@@ -296,6 +300,9 @@ struct swps_table {
   // batch, the candidate subset's row indices, the local / gathered [nq][k] answers, the
   // analogy's a / b / c rows with presence flags, its queries and exclusion lists
   swps::DevMem nn_cand, nn_idx, nn_part, nn_abc, nn_q, nn_excl;
+  // repeated-key calls (swps_dup.hip), grow-only: the coalesce's sort buffers and maps, the
+  // distinct keys' rows, the (run, chunk) items, the chunk partials, the routed forms' buffers
+  swps::DevMem dup[swps::kDupBufs];
 };
 
 namespace swps {
