@@ -241,6 +241,67 @@ int swps_push_dup(swps_table *t, const uint64_t *d_keys, uint64_t n, const void 
 int swps_lookup_h(swps_table *t, const uint64_t *keys, uint64_t n, int32_t insert, void *vals, uint8_t *found);
 int swps_push_dup_h(swps_table *t, const uint64_t *keys, uint64_t n, const void *grads, int32_t reduce,
                     double scale);
+
+/* ---- pooled lookups: one row per BAG of ids (swps_bag.hip) --
+ * The sum of a sample's feature embeddings, the mean of a sentence's word vectors, the weighted sum
+ * of a sparse LR sample: d_keys[n] as above (repeats allowed, ~0 is padding) and d_offsets[nbags + 1]
+ * in CSR form: offsets[0] = 0, offsets[nbags] = n, never decreasing; bag b is the positions
+ * [offsets[b], offsets[b + 1]) and may be empty.  The MEMBERS of a bag are its non-padding
+ * positions, m_b their number.  d_weights: NULL, or one fp64 weight per position (SWPS_BAG_SUM only).
+ * Neither call materialises a per-position tensor.
+ *
+ * Checked before any device call: a null table or pointer, a bad mode / insert / gdtype, weights
+ * with SWPS_BAG_MEAN, an LR table with gdtype != SWPS_F32 -> SWPS_E_CFG; n or nbags >= 2^32 ->
+ * SWPS_E_UNSUPPORTED; nbags == 0 with n != 0 -> SWPS_E_CFG.  The offsets are checked ON THE DEVICE
+ * and the verdict comes with the one host read the call makes anyway, BEFORE any key is inserted or
+ * any row changed: a violation returns SWPS_E_CFG naming the first bad bag and leaves the table as
+ * it was.  Streams, the single host read plus synchronise, the latched-error ending and n == 0 are
+ * those of the repeated-key calls (nbags == 0 returns SWPS_OK; a routed table still joins the
+ * exchange).
+ *
+ * swps_lookup_bag: d_out[b] = the pooled pull value of bag b ([nbags][pull elems], table dtype).
+ *   Let val(p) be what swps_lookup returns at position p (insert = 0: an absent key is a zero row
+ *   that still counts as a member).  Per element e, in fp64 whatever the table dtype:
+ *     term(p) = (double)val(p)[e]            without weights
+ *     term(p) = (double)val(p)[e] * w[p]     with weights (one multiply)
+ *   A bag is cut into chunks of SWPS_DUP_CHUNK consecutive POSITIONS (chunk c covers offsets[b] +
+ *   128 c ...; by position, so the chunks follow from the offsets alone).  A chunk's sum is the
+ *   sequential chain of its members' terms in ascending position, starting FROM THE FIRST MEMBER
+ *   (not from 0.0); a chunk without members is skipped; the chunk sums are chained in chunk order
+ *   from the first chunk that has members; SWPS_BAG_MEAN divides once by (double)m_b; the result is
+ *   cast to the table dtype once.  m_b = 0 gives +0.0 everywhere (no division).  A key that occurs
+ *   twice in a bag counts twice.  This order is part of the ABI.
+ *   insert = 1 inserts every absent distinct key once, exactly as swps_lookup does (same init
+ *   order, growth rule and latches); padding is skipped, not refused.
+ *
+ * swps_push_bag: d_bag_grads is G[nbags][push elems] of gdtype.  With b(p) the bag of position p,
+ *   per element
+ *     term(p) = (double)G[b(p)][e]                       SWPS_BAG_SUM without weights
+ *     term(p) = (double)G[b(p)][e] * w[p]                SWPS_BAG_SUM with weights
+ *     term(p) = (double)G[b(p)][e] / (double)m_b(p)      SWPS_BAG_MEAN
+ *   (one IEEE operation each), and the terms of each distinct key's occurrences are combined
+ *   EXACTLY as swps_push_dup(SWPS_REDUCE_SUM, scale) combines an fp64 [n][push elems] gradient; the
+ *   key takes one step of the push rule (LR: the combined gradient rounded to fp32 first).  So on
+ *   a W2V table swps_push_bag leaves the table bit-identical to swps_push_dup fed the expanded fp64
+ *   matrix.  Padding positions are skipped; an unknown key latches SWPS_E_BADKEY after the other
+ *   keys were applied.
+ *
+ * Routed tables: both calls are COLLECTIVE (coalesce, the routed pull of the distinct keys, pooled
+ * through d_inv; reduce to one gradient per distinct key in the wire type, then the routed push):
+ * only distinct keys cross the wire.  insert = 0 is local only (SWPS_E_UNSUPPORTED).  A rank whose
+ * offsets are refused has left the collective: the caller's contract, as for any refused argument.
+ * The _h forms take host arrays in the wire types (W2V fp64, LR fp32). */
+#define SWPS_BAG_SUM 0
+#define SWPS_BAG_MEAN 1
+int swps_lookup_bag(swps_table *t, const uint64_t *d_keys, uint64_t n, const uint64_t *d_offsets, uint64_t nbags,
+                    const double *d_weights, int32_t mode, int32_t insert, void *d_out, void *stream);
+int swps_push_bag(swps_table *t, const uint64_t *d_keys, uint64_t n, const uint64_t *d_offsets, uint64_t nbags,
+                  const double *d_weights, int32_t mode, const void *d_bag_grads, int32_t gdtype, double scale,
+                  void *stream);
+int swps_lookup_bag_h(swps_table *t, const uint64_t *keys, uint64_t n, const uint64_t *offsets, uint64_t nbags,
+                      const double *weights, int32_t mode, int32_t insert, void *out);
+int swps_push_bag_h(swps_table *t, const uint64_t *keys, uint64_t n, const uint64_t *offsets, uint64_t nbags,
+                    const double *weights, int32_t mode, const void *bag_grads, double scale);
 /* Overwrite / read full rows (table dtype, d_rows[n][row elems]). */
 int swps_assign(swps_table *t, const uint64_t *d_keys, uint64_t n, const void *d_rows);
 int swps_export(swps_table *t, const uint64_t *d_keys, uint64_t n, void *d_rows);

@@ -269,8 +269,16 @@ class Table:
 
     @staticmethod
     def _stream(x):
+        """torch's current stream of x's device, for the calls that take one.  Torch's default
+        stream has the handle 0, which the library reads as "the table's own stream", and that
+        stream (non-blocking) is not ordered after work queued on torch's default stream: wait
+        for it here, so inputs a torch kernel is still writing are complete (the calls
+        synchronise before they return anyway)."""
         import torch
-        return ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        s = torch.cuda.current_stream(x.device)
+        if not s.cuda_stream:
+            s.synchronize()
+        return ctypes.c_void_p(s.cuda_stream)
 
     def coalesce(self, keys):
         """keys: an int64 CUDA tensor of any shape; keys may repeat, -1 (~0) is padding.
@@ -341,6 +349,88 @@ class Table:
         if g.size != len(k) * self.push_elems:
             raise ValueError("grads must hold push_elems values per key")
         check(lib.swps_push_dup_h(self.h, ptr(k), len(k), ptr(g), self._REDUCE[reduce], float(scale)))
+
+    # ---- pooled lookups (swps_lookup_bag / swps_push_bag) ----
+    _BAG = {"sum": capi.BAG_SUM, "mean": capi.BAG_MEAN, 0: 0, 1: 1}
+
+    def _bag_args(self, keys, offsets, weights, mode):
+        """(on_device, keys [n], offsets [nbags + 1], fp64 weights [n] or None) of the call's kind."""
+        if mode not in self._BAG:
+            raise ValueError("mode is 'sum' or 'mean'")
+        if hasattr(keys, "data_ptr"):
+            import torch
+            if keys.dtype != torch.int64 or not hasattr(offsets, "data_ptr") or offsets.dtype != torch.int64:
+                raise TypeError("keys and offsets must be int64 tensors")
+            k = keys.contiguous().view(-1)
+            off = offsets.to(k.device).contiguous().view(-1)
+            w = None
+            if weights is not None:
+                if not weights.dtype.is_floating_point:
+                    raise TypeError("weights must be a floating-point tensor")
+                w = weights.to(device=k.device, dtype=torch.float64).contiguous().view(-1)  # exact; 8 n bytes
+                if w.numel() != k.numel():
+                    raise ValueError("weights must hold one value per key")
+            if off.numel() < 1:
+                raise ValueError("offsets must hold nbags + 1 entries")
+            return True, k, off, w
+        k = np.ascontiguousarray(self._keys_like(keys, False, None).reshape(-1))
+        off = np.ascontiguousarray(np.asarray(offsets).reshape(-1)).astype(np.uint64)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+            if len(w) != len(k):
+                raise ValueError("weights must hold one value per key")
+        if len(off) < 1:
+            raise ValueError("offsets must hold nbags + 1 entries")
+        return False, k, off, w
+
+    def lookup_bag(self, keys, offsets, weights=None, mode="sum", insert=True):
+        """One pooled row per bag -> [nbags, pull_elems]: the sum (mode="mean": the mean over the
+        bag's members) of the pull values of keys[offsets[b]:offsets[b + 1]], times weights[p] when
+        given (sum only), accumulated in fp64 in the defined order of swps_lookup_bag (chunks of
+        128 positions, each a chain from its first member) and cast to the table dtype once.
+        offsets: nbags + 1 CSR entries (first 0, last n, never decreasing); -1 (~0) keys are padding;
+        an empty bag is a zero row.  CUDA int64 tensors run on torch's current stream (weights of
+        any float dtype are converted to fp64 on the device); numpy arrays take the host form
+        (wire types: W2V fp64, LR fp32).  insert=True inserts every absent distinct key once, as
+        `lookup` does; insert=False pools an absent key as a zero row that still counts."""
+        dev, k, off, w = self._bag_args(keys, offsets, weights, mode)
+        lib, nb = capi.lib(), len(off) - 1
+        if dev:
+            import torch
+            out = torch.empty((nb, self.pull_elems), dtype=self.torch_dtype, device=k.device)
+            check(lib.swps_lookup_bag(self.h, ptr(k), k.numel(), ptr(off), nb, ptr(w), self._BAG[mode], int(insert),
+                                      ptr(out), self._stream(k)))
+            return out
+        out = np.zeros((nb, self.pull_elems), dtype=np.float64 if self.layout == "w2v" else np.float32)
+        check(lib.swps_lookup_bag_h(self.h, ptr(k), len(k), ptr(off), nb, ptr(w), self._BAG[mode], int(insert),
+                                    ptr(out)))
+        return out
+
+    def push_bag(self, keys, offsets, bag_grads, weights=None, mode="sum", scale=1.0):
+        """The backward of `lookup_bag`: one step of the push rule per DISTINCT key.  bag_grads:
+        [nbags, push_elems], fp32 or fp64 (LR tables: fp32).  Every occurrence of a key inherits
+        its bag's gradient row (times weights[p]; mode="mean": divided by the bag's member count),
+        and a key's terms are combined exactly as `push_dup(reduce="sum", scale)` combines the
+        expanded fp64 [n, push_elems] matrix, which is never built.  Padding is skipped; a key the
+        table lacks raises SWPS_E_BADKEY after the other keys were applied."""
+        dev, k, off, w = self._bag_args(keys, offsets, weights, mode)
+        lib, nb = capi.lib(), len(off) - 1
+        if dev:
+            import torch
+            g = bag_grads.contiguous()
+            if g.dtype not in (torch.float32, torch.float64):
+                raise TypeError("bag_grads must be float32 or float64")
+            if g.numel() != nb * self.push_elems:
+                raise ValueError("bag_grads must hold push_elems values per bag")
+            gd = capi.F64 if g.dtype == torch.float64 else capi.F32
+            check(lib.swps_push_bag(self.h, ptr(k), k.numel(), ptr(off), nb, ptr(w), self._BAG[mode], ptr(g), gd,
+                                    float(scale), self._stream(k)))
+            return
+        g = np.ascontiguousarray(bag_grads, dtype=np.float64 if self.layout == "w2v" else np.float32)
+        if g.size != nb * self.push_elems:
+            raise ValueError("bag_grads must hold push_elems values per bag")
+        check(lib.swps_push_bag_h(self.h, ptr(k), len(k), ptr(off), nb, ptr(w), self._BAG[mode], ptr(g), float(scale)))
 
     # ---- top-k queries (swps_nearest / swps_analogy; collective on a routed table) ----
     _PARTS = {"h": 0, "v": 1, 0: 0, 1: 1}

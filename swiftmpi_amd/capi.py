@@ -25,6 +25,7 @@ METRIC_DOT, METRIC_COS = 0, 1
 NEAREST_MAX_K, NEAREST_MAX_EXCL = 64, 8
 REDUCE_SUM, REDUCE_MEAN = 0, 1
 DUP_CHUNK = 128
+BAG_SUM, BAG_MEAN = 0, 1
 COMM_ID_BYTES = 128
 
 # swps_transport callbacks (host all-gather / all-to-all-v)
@@ -95,6 +96,10 @@ PROTOS = {
     "swps_push_dup": (ctypes.c_int, [_p, _p, _u64, _p, _i32, _i32, ctypes.c_double, _p]),
     "swps_lookup_h": (ctypes.c_int, [_p, _p, _u64, _i32, _p, _p]),
     "swps_push_dup_h": (ctypes.c_int, [_p, _p, _u64, _p, _i32, ctypes.c_double]),
+    "swps_lookup_bag": (ctypes.c_int, [_p, _p, _u64, _p, _u64, _p, _i32, _i32, _p, _p]),
+    "swps_push_bag": (ctypes.c_int, [_p, _p, _u64, _p, _u64, _p, _i32, _p, _i32, ctypes.c_double, _p]),
+    "swps_lookup_bag_h": (ctypes.c_int, [_p, _p, _u64, _p, _u64, _p, _i32, _i32, _p]),
+    "swps_push_bag_h": (ctypes.c_int, [_p, _p, _u64, _p, _u64, _p, _i32, _p, ctypes.c_double]),
     "swps_comm_unique_id": (ctypes.c_int, [_p]),
     "swps_comm_bootstrap_tcp": (ctypes.c_int, [ctypes.c_char_p, _i32, _i32, _i32, _i32, _p]),
     "swps_comm_create_rccl": (ctypes.c_int, [_p, _i32, _i32, _i32, ctypes.POINTER(_p)]),
