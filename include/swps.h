@@ -144,10 +144,66 @@ int swps_table_sync(swps_table *t);
  *   by itself (the fixed-capacity contract holds) and swps_table_reserve fails with SWPS_E_STATE.
  *   So a word2vec / LR table may start small under a ceiling: init grows it to the vocabulary.
  *
- * swps_table_capacity: out4 = {capacity, max_capacity, slots, growths so far}. */
+ * swps_table_capacity: out4 = {capacity, max_capacity, slots, growths so far}.  `growths` counts
+ *   MOVES of the shard: every growth and every swps_table_shrink that changed the capacity. */
 int swps_table_reserve(swps_table *t, uint64_t keys);
 int swps_table_set_max_capacity(swps_table *t, uint64_t max_keys);
 int swps_table_capacity(swps_table *t, uint64_t *out4);
+/* ---- removing keys (swps_erase.hip) ----
+ * The reference's dense_hash_map shards are never erased from (sparsetable.h has no erase): an
+ * extension, and the other half of growth, so a table that serves streaming ids under a ceiling
+ * need not be exported and rebuilt through caller memory once it is full.
+ *
+ * swps_erase(t, d_keys, n, erased): removes the listed keys (device array; swps_erase_h: a host
+ *   array, staged).  The list may repeat keys, name keys the shard does not hold and hold ~0: all
+ *   ignored.  n == 0 is legal.  *erased (may be NULL) = the DISTINCT keys removed.  The call
+ *   synchronises the device (as swps_table_reserve: async forms may have used caller streams).
+ *   Afterwards
+ *     - swps_table_size has dropped by *erased; a removed key behaves as never seen: swps_push
+ *       latches SWPS_E_BADKEY, swps_lookup(insert = 0) and swps_table_find_h report it absent,
+ *       swps_nearest / swps_analogy never return it, and a later pull runs init_param afresh (zero
+ *       accumulators);
+ *     - every surviving key keeps its row contents bit for bit, but row INDICES may change: the
+ *       rows are compacted by the rule of swps_erase_plan below (at most min(#erased, #survivors)
+ *       rows move, never the table), so swps_table_keys after the call is a deterministic
+ *       function of swps_table_keys before it.  Because contexts hold row indices, a table pinned
+ *       by an app context (above) returns SWPS_E_STATE and is left unchanged;
+ *     - the freed rows are reusable: a fixed-capacity table that was full takes *erased new keys
+ *       without SWPS_E_OOM.  Slots an earlier overflow claimed without a row are dropped and the
+ *       row count is clamped, as swps_table_reserve does: an erase after an SWPS_E_OOM repairs
+ *       the table;
+ *     - the latched error flag, the snapshot checksum, the route, the SWPS_INIT_FLCG draw state,
+ *       capacity, max_capacity and growths are untouched; the host bound on the row count of a
+ *       growable table restarts at the new count.
+ *   Cost: the hash index is REBUILT from the surviving rows (a 0xFF fill of the slot arrays, 12
+ *   bytes per slot, and one re-insert per survivor), not tombstoned: the table has no spare key
+ *   value for a tombstone (0 and 2^64 - 2 are legal keys) and the insert kernel every training
+ *   step runs stays as it is.  So each call that removes a key pays a term proportional to the
+ *   slot count, whatever n is: batch your erases.  A call that removes nothing from a table that
+ *   never overflowed changes nothing and rebuilds nothing.  Shards of 2^31 rows or more ->
+ *   SWPS_E_UNSUPPORTED; n >= 2^32 -> SWPS_E_UNSUPPORTED.
+ *   On a routed table swps_erase is COLLECTIVE, like swps_pull / swps_push: every rank calls it
+ *   (n = 0 allowed; swps_finish serves the other ranks' erases), the keys travel to their owners
+ *   (no values, no reply), each owner erases what it received (two ranks may name the same key)
+ *   and *erased is the count removed from the LOCAL shard.  swps_erase_h on a routed table ->
+ *   SWPS_E_UNSUPPORTED.
+ *
+ * swps_prune(t, max_g2, erased): removes every key whose row is COLD: every AdaGrad accumulator
+ *   element (W2V: h2sum and v2sum; LR: grad2sum) is <= max_g2.  The test is max <= threshold:
+ *   exact and independent of any summation order.  A row with a NaN accumulator is kept.
+ *   max_g2 = 0 means "never received a non-zero gradient".  A NaN max_g2 -> SWPS_E_CFG; an
+ *   SWPS_PUSH_SGD table never touches the accumulators -> SWPS_E_UNSUPPORTED.  Everything else as
+ *   swps_erase; on a routed table the call is local to the shard, like swps_table_reserve.
+ *
+ * swps_table_shrink(t, keys): capacity = max(keys, rows held, 1) when that is below the current
+ *   capacity, else a no-op.  A move like swps_table_reserve's (new buffers, peak footprint old +
+ *   new, every key, row and row index kept, counted in `growths`): a failed allocation leaves the
+ *   table unchanged, a pinned table returns SWPS_E_STATE.  A ceiling stays valid (it only has to
+ *   be >= the capacity).  Local on a routed table. */
+int swps_erase(swps_table *t, const uint64_t *d_keys, uint64_t n, uint64_t *erased);
+int swps_erase_h(swps_table *t, const uint64_t *keys, uint64_t n, uint64_t *erased);
+int swps_prune(swps_table *t, double max_g2, uint64_t *erased);
+int swps_table_shrink(swps_table *t, uint64_t keys);
 /* per-key element counts of a full row / a pull value / a push value */
 int swps_table_row_elems(swps_table *t, int32_t *row, int32_t *pull, int32_t *push);
 
@@ -652,6 +708,16 @@ int swps_glibc_rand(uint32_t seed, uint64_t skip, uint64_t n, int32_t *out);
  * capacity 0 or a capacity / ceiling >= 0xFFFFFFF0 -> SWPS_E_CFG. */
 int swps_grow_plan(uint64_t capacity, uint64_t max_capacity, uint64_t nrows, uint64_t incoming,
                    uint64_t *new_capacity, uint64_t *new_slots);
+/* the compaction rule of swps_erase / swps_prune for a shard of nrows rows of
+ * which dead[r] != 0 are removed: M = nrows - #dead survive (*survivors).  The HOLES are the dead
+ * rows r < M and the MOVERS the live rows r >= M, both ascending and equally many (*moves); the
+ * k-th mover is copied into the k-th hole (dst[k] = the hole, src[k] = the mover), every other row
+ * stays.  So every src >= M > every dst (an in-place, race-free copy), moves <= min(#dead, M), and
+ * the row order after an erase is a function of the order before it.  src / dst have room for
+ * `cap` entries: cap < moves -> SWPS_E_CFG (with *survivors and *moves set); nrows >= 2^32 ->
+ * SWPS_E_CFG.  Any output may be NULL. */
+int swps_erase_plan(const uint8_t *dead, uint64_t nrows, uint64_t *survivors, uint32_t *src, uint32_t *dst,
+                    uint64_t cap, uint64_t *moves);
 
 /* ---- sent2vec (apps/sent2vec/sent2vec.cpp on apps/word2vec/word2vec.h) ---
  * Sentence vectors against frozen word vectors: Sent2Vec::train

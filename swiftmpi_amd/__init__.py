@@ -24,7 +24,7 @@ from . import capi
 from .capi import SwpsError, check, ptr
 
 __all__ = ["Table", "Word2Vec", "Sent2Vec", "LR", "Config", "SwpsError", "bkdr", "fmix64", "hashfrag_table",
-           "to_node_id", "load_library", "grow_plan"]
+           "to_node_id", "load_library", "grow_plan", "erase_plan"]
 
 
 def load_library():
@@ -76,6 +76,18 @@ def grow_plan(capacity, max_capacity, nrows, incoming):
     nc, ns = ctypes.c_uint64(), ctypes.c_uint64()
     check(capi.lib().swps_grow_plan(capacity, max_capacity, nrows, incoming, ctypes.byref(nc), ctypes.byref(ns)))
     return nc.value, ns.value
+
+
+def erase_plan(dead):
+    """The compaction rule of an erase (swps_erase_plan, host only): dead[r] != 0 marks the rows to
+    remove -> (survivors M, src, dst): the live rows src[k] >= M move into the dead rows dst[k] < M,
+    both ascending; every other row stays."""
+    d = np.ascontiguousarray(np.asarray(dead).reshape(-1) != 0, dtype=np.uint8)
+    m, h = ctypes.c_uint64(), ctypes.c_uint64()
+    src = np.zeros(max(len(d) // 2, 1), dtype=np.uint32)  # moves <= min(#dead, M) <= N / 2
+    dst = np.zeros_like(src)
+    check(capi.lib().swps_erase_plan(ptr(d), len(d), ctypes.byref(m), ptr(src), ptr(dst), len(src), ctypes.byref(h)))
+    return m.value, src[:h.value], dst[:h.value]
 
 
 class Config:
@@ -191,6 +203,55 @@ class Table:
         out = np.zeros(4, dtype=np.uint64)
         check(capi.lib().swps_table_capacity(self.h, ptr(out)))
         return dict(zip(["capacity", "max_capacity", "slots", "growths"], (int(x) for x in out)))
+
+    # ---- removal (swps_erase / swps_prune / swps_table_shrink) ----
+    def erase(self, keys):
+        """Remove the listed keys -> the number of distinct keys removed from the local shard.
+        keys: an int64 CUDA tensor or an integer numpy array / sequence, of any shape; repeats,
+        keys the table lacks and -1 (~0) are ignored.  Survivors keep their rows bit for bit but
+        may change row index (`keys()` follows `erase_plan`), so SWPS_E_STATE while an app context
+        holds the table.  The hash index is rebuilt on every call that removes a key (a cost
+        proportional to the slot count): batch the keys.  Collective on a routed table (tensor
+        keys only), where the count is this rank's shard's."""
+        n = ctypes.c_uint64()
+        if hasattr(keys, "data_ptr"):
+            import torch
+            if keys.dtype != torch.int64:
+                raise TypeError("keys must be an int64 tensor")
+            k = keys.contiguous().view(-1)
+            if k.numel() and not k.is_cuda:
+                raise TypeError("tensor keys must live on the table's device (pass a numpy array for host keys)")
+            if k.numel():
+                self._stream(k)  # the keys are complete before the table's own stream reads them
+            check(capi.lib().swps_erase(self.h, ptr(k), k.numel(), ctypes.byref(n)))
+            return n.value
+        a = np.asarray(keys)
+        if a.size and a.dtype.kind not in "iu":
+            raise TypeError("keys must be integers, not %s" % a.dtype)
+        k = np.ascontiguousarray(self._keys_like(a.reshape(-1) if a.size else np.zeros(0, np.uint64), False, None))
+        check(capi.lib().swps_erase_h(self.h, ptr(k), len(k), ctypes.byref(n)))
+        return n.value
+
+    def prune(self, max_g2=0.0):
+        """Remove every key whose AdaGrad accumulators (w2v: h2sum and v2sum; lr: grad2sum) are all
+        <= max_g2 -> the number removed.  0.0: the keys that never received a non-zero gradient.
+        A row with a NaN accumulator is kept.  Local to the shard; otherwise as `erase`."""
+        if isinstance(max_g2, bool) or not isinstance(max_g2, (int, float, np.integer, np.floating)):
+            raise TypeError("max_g2 must be a real number")
+        max_g2 = float(max_g2)
+        if max_g2 != max_g2 or max_g2 < 0:
+            raise ValueError("max_g2 must be >= 0 (the accumulators are sums of squares), not %r" % max_g2)
+        n = ctypes.c_uint64()
+        check(capi.lib().swps_prune(self.h, max_g2, ctypes.byref(n)))
+        return n.value
+
+    def shrink(self, keys=0):
+        """Capacity = max(keys, rows held, 1) when that is below the current capacity (a move, as
+        `reserve`: counted in `growths`, SWPS_E_STATE while pinned); otherwise nothing happens."""
+        keys = int(keys)
+        if keys < 0:
+            raise ValueError("keys must be >= 0")
+        check(capi.lib().swps_table_shrink(self.h, keys))
 
     def pull(self, keys):
         """keys: int64/uint64 CUDA tensor of distinct keys -> [n, pull_elems] tensor."""

@@ -85,6 +85,11 @@ PROTOS = {
     "swps_table_set_max_capacity": (ctypes.c_int, [_p, _u64]),
     "swps_table_capacity": (ctypes.c_int, [_p, _p]),
     "swps_grow_plan": (ctypes.c_int, [_u64, _u64, _u64, _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "swps_erase": (ctypes.c_int, [_p, _p, _u64, ctypes.POINTER(_u64)]),
+    "swps_erase_h": (ctypes.c_int, [_p, _p, _u64, ctypes.POINTER(_u64)]),
+    "swps_prune": (ctypes.c_int, [_p, ctypes.c_double, ctypes.POINTER(_u64)]),
+    "swps_table_shrink": (ctypes.c_int, [_p, _u64]),
+    "swps_erase_plan": (ctypes.c_int, [_p, _u64, ctypes.POINTER(_u64), _p, _p, _u64, ctypes.POINTER(_u64)]),
     "swps_table_row_elems": (ctypes.c_int, [_p, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "swps_pull": (ctypes.c_int, [_p, _p, _u64, _p]),
     "swps_push": (ctypes.c_int, [_p, _p, _u64, _p]),

@@ -118,7 +118,7 @@ struct swps_comm {
 
 namespace {
 
-enum { kOpPull = 0, kOpPush = 1, kOpFinish = 2 };
+enum { kOpPull = 0, kOpPush = 1, kOpFinish = 2, kOpErase = 3 };
 
 // a non-blocking communicator may answer ncclInProgress: the call is queued (comm_settle waits)
 #define SWPS_NCCL(call)                                                                                   \
@@ -319,7 +319,8 @@ __global__ void k_scatter_rows(const uint32_t *__restrict__ perm, uint64_t n, co
 }
 
 // One round.  op: kOpPull (d_io = values out, table dtype [n][pull elems]),
-// kOpPush (d_io = mean gradients in, the push wire type [n][push elems]) or
+// kOpPush (d_io = mean gradients in, the push wire type [n][push elems]),
+// kOpErase (d_io unused: only keys travel, the owner's count lands in t->er_last) or
 // kOpFinish (n = 0).  Returns the op every active rank ran (or kOpFinish when
 // all ranks are finishing) in *ran.
 int route_round(swps_table *t, int op, const uint64_t *d_keys, uint64_t n, void *d_io, hipStream_t s, int *ran) {
@@ -368,7 +369,7 @@ int route_round(swps_table *t, int op, const uint64_t *d_keys, uint64_t n, void 
     const int o = (int)all[(size_t)r * (2 + world)];
     if (o == kOpFinish) continue;
     if (agreed != kOpFinish && agreed != o)
-      return fail(SWPS_E_STATE, "ranks disagree on the routed call (one pulls while another pushes)");
+      return fail(SWPS_E_STATE, "ranks disagree on the routed call (pull, push and erase rounds do not mix)");
     agreed = o;
   }
   *ran = agreed;
@@ -391,6 +392,19 @@ int route_round(swps_table *t, int op, const uint64_t *d_keys, uint64_t n, void 
   };
   SWPS_TRY(comm_alltoallv(t->comm, keys_s, scaled(send_k, 8), t->r_rkeys.p, scaled(recv_k, 8), s, t->stage,
                           "routed keys"));
+  if (agreed == kOpErase) {
+    // ---- 4. owner: the local erase of what it received (the same key from several ranks, keys
+    // the shard lacks: harmless); no values, no reply ----
+    t->rstats[0]++;
+    t->rstats[1] += n;
+    t->rstats[2] += remote;
+    t->rstats[3] += n * 8;
+    t->rstats[4] += remote * 8;
+    t->rstats[5] += nrecv;
+    t->er_last = 0;
+    if (nrecv) SWPS_TRY(table_erase_keys(t, t->r_rkeys.as<uint64_t>(), nrecv, &t->er_last, s));
+    return SWPS_OK;
+  }
   const size_t vb = agreed == kOpPull ? pb : gb;
   SWPS_TRY(t->r_rows.ensure(std::max<uint64_t>(nrecv, 1) * 4));
   SWPS_TRY(t->r_rbuf.ensure(std::max<uint64_t>(nrecv, 1) * vb));
@@ -892,6 +906,19 @@ int routed_push(swps_table *t, const uint64_t *d_keys, uint64_t n, const void *d
   int ran = 0;
   SWPS_TRY(route_round(t, kOpPush, d_keys, n, const_cast<void *>(d_grads), s, &ran));
   if (ran != kOpPush) return fail(SWPS_E_STATE, "routed push while every other rank has finished");
+  return SWPS_OK;
+}
+
+int routed_erase(swps_table *t, const uint64_t *d_keys, uint64_t n, uint64_t *erased, hipStream_t s) {
+  if (erased) *erased = 0;
+  if (t->finished) return fail(SWPS_E_STATE, "erase after swps_finish");
+  if (t->pins)  // before the round: the other ranks' rounds are served by this rank's next call
+    return fail(SWPS_E_STATE, "an app context holds this table's row indices: no key can be removed meanwhile");
+  int ran = 0;
+  SWPS_TRY(route_round(t, kOpErase, d_keys, n, nullptr, s, &ran));
+  if (ran != kOpErase) return fail(SWPS_E_STATE, "routed erase while every other rank has finished");
+  SWPS_HIP(hipStreamSynchronize(s));
+  if (erased) *erased = t->er_last;
   return SWPS_OK;
 }
 

@@ -279,4 +279,28 @@ int swps_grow_plan(uint64_t capacity, uint64_t max_capacity, uint64_t nrows, uin
   return SWPS_OK;
 }
 
+// The compaction rule of an erase (swps_erase.hip runs the same rule from a prefix sum of `dead`):
+// the live rows at or past the survivor count fill the dead rows below it, both in ascending order.
+int swps_erase_plan(const uint8_t *dead, uint64_t nrows, uint64_t *survivors, uint32_t *src, uint32_t *dst,
+                    uint64_t cap, uint64_t *moves) {
+  if (nrows && !dead) return swps::fail(SWPS_E_CFG, "null argument");
+  if (nrows >= (1ULL << 32)) return swps::fail(SWPS_E_CFG, "row indices are 32-bit");
+  uint64_t ndead = 0;
+  for (uint64_t r = 0; r < nrows; r++) ndead += dead[r] != 0;
+  const uint64_t M = nrows - ndead;
+  uint64_t H = 0;
+  for (uint64_t r = 0; r < M; r++) H += dead[r] != 0;
+  if (survivors) *survivors = M;
+  if (moves) *moves = H;
+  if (cap < H) return swps::fail(SWPS_E_CFG, "plan buffers hold " + std::to_string(cap) + " moves; the plan has " +
+                                                 std::to_string(H));
+  uint64_t k = 0;
+  for (uint64_t r = 0; r < M && dst; r++)
+    if (dead[r]) dst[k++] = (uint32_t)r;
+  k = 0;
+  for (uint64_t r = M; r < nrows && src; r++)
+    if (!dead[r]) src[k++] = (uint32_t)r;
+  return SWPS_OK;
+}
+
 }  // extern "C"

@@ -303,6 +303,10 @@ struct swps_table {
   // repeated-key calls (swps_dup.hip), grow-only: the coalesce's sort buffers and maps, the
   // distinct keys' rows, the (run, chunk) items, the chunk partials, the routed forms' buffers
   swps::DevMem dup[swps::kDupBufs];
+  // swps_erase / swps_prune (swps_erase.hip), grow-only: the listed keys' rows, the per-row dead
+  // flags, their prefix sum with its temporary storage, the compaction's (mover, hole) pairs
+  swps::DevMem er_rows, er_dead, er_scan, er_tmp, er_src, er_dst;
+  uint64_t er_last = 0;  // the local shard's count of the last routed erase round (route_round)
 };
 
 namespace swps {
@@ -318,6 +322,12 @@ int table_find_or_insert_placed(swps_table *t, const uint64_t *d_keys, uint64_t 
 int table_lookup(swps_table *t, const uint64_t *d_keys, uint64_t n, uint32_t *d_rows_out, hipStream_t s);
 int table_probe(swps_table *t, const uint64_t *d_keys, uint64_t n, uint32_t *d_rows_out, hipStream_t s);
 int table_check_error(swps_table *t, hipStream_t s);
+// the hash index of rows [0, nrows) rebuilt from row_key, ordered on s: a 0xFF fill of keys and
+// slot_row, then k_rehash; whatever the slots held before (kFullRow leftovers included) is gone
+int table_rebuild_index(swps_table *t, uint64_t nrows, hipStream_t s);
+// swps_erase on the local shard (swps_erase.hip); the routed form's owner side
+int table_erase_keys(swps_table *t, const uint64_t *d_keys, uint64_t n, uint64_t *erased, hipStream_t s);
+int routed_erase(swps_table *t, const uint64_t *d_keys, uint64_t n, uint64_t *erased, hipStream_t s);
 // an app context whose init completed holds row indices and reads t->rows at every launch: while
 // any context pins the table it neither grows by itself nor may be reserved
 void table_pin(swps_table *t);

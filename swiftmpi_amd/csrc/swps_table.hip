@@ -586,8 +586,20 @@ void table_unpin(swps_table *t) {
   t->rows_bound = t->cfg.capacity;  // not kept while pinned: the next insert reads the real count
 }
 
-// The move: a shard of new_cap >= cfg.capacity rows with every key, row and row
-// index of this one.  New buffers of exactly the new sizes, the index rebuilt by k_rehash from
+int table_rebuild_index(swps_table *t, uint64_t nrows, hipStream_t s) {
+  SWPS_HIP(hipMemsetAsync(t->keys.p, 0xFF, t->nslots * 8, s));
+  SWPS_HIP(hipMemsetAsync(t->slot_row.p, 0xFF, t->nslots * 4, s));
+  if (nrows) {
+    k_rehash<<<blocks_for(nrows), 256, 0, s>>>(t->row_key.as<uint64_t>(), nrows, t->keys.as<uint64_t>(),
+                                                t->slot_row.as<uint32_t>(), t->mask);
+    SWPS_HIP(hipGetLastError());
+  }
+  return SWPS_OK;
+}
+
+// The move: a shard of new_cap rows (more than cfg.capacity: a growth; fewer
+// but at least the rows held: swps_table_shrink) with every key, row and row index of this one.
+// New buffers of exactly the new sizes, the index rebuilt by k_rehash from
 // row_key, row_key and rows copied device to device; the table's own buffers are swapped in only
 // after everything has completed, so any failure leaves the table as it was.  Slots an overflow
 // left as kFullRow have no row and are not carried over; the row counter is clamped to the old
@@ -597,6 +609,7 @@ static int table_move(swps_table *t, uint64_t new_cap) {
   uint32_t cnt = 0;
   SWPS_HIP(hipMemcpy(&cnt, t->counters.p, 4, hipMemcpyDeviceToHost));
   const uint32_t nrows = cnt > t->cfg.capacity ? (uint32_t)t->cfg.capacity : cnt;
+  if (new_cap < nrows || new_cap == 0) return fail(SWPS_E_CFG, "a move below the rows held");
   uint64_t ns = 1;
   while (ns < 2 * new_cap) ns <<= 1;
   const size_t rb = (size_t)t->row_elems * t->esize;
@@ -1060,6 +1073,21 @@ int swps_table_reserve(swps_table *t, uint64_t keys) {
   if (keys <= t->cfg.capacity) return SWPS_OK;
   SWPS_HIP(hipSetDevice(t->cfg.device));
   return table_move(t, keys);
+}
+
+int swps_table_shrink(swps_table *t, uint64_t keys) {
+  if (!t) return fail(SWPS_E_CFG, "null table");
+  if (t->pins)
+    return fail(SWPS_E_STATE, "an app context holds this table's rows (from its init to its destroy): the "
+                              "capacity is fixed meanwhile");
+  if (keys >= t->cfg.capacity) return SWPS_OK;
+  SWPS_HIP(hipSetDevice(t->cfg.device));
+  SWPS_HIP(hipDeviceSynchronize());  // the row count below must include every async insert
+  uint32_t cnt = 0;
+  SWPS_HIP(hipMemcpy(&cnt, t->counters.p, 4, hipMemcpyDeviceToHost));
+  const uint64_t target = std::max<uint64_t>(std::max<uint64_t>(keys, std::min<uint64_t>(cnt, t->cfg.capacity)), 1);
+  if (target >= t->cfg.capacity) return SWPS_OK;
+  return table_move(t, target);
 }
 
 int swps_table_set_max_capacity(swps_table *t, uint64_t max_keys) {
