@@ -358,6 +358,72 @@ int swps_lookup_bag_h(swps_table *t, const uint64_t *keys, uint64_t n, const uin
                       const double *weights, int32_t mode, int32_t insert, void *out);
 int swps_push_bag_h(swps_table *t, const uint64_t *keys, uint64_t n, const uint64_t *offsets, uint64_t nbags,
                     const double *weights, int32_t mode, const void *bag_grads, double scale);
+
+/* ---- admission by count: a count-min gate on the inserting lookups (swps_admit.hip)
+ * In a stream of ids most ids occur once or twice, and every inserting lookup gives each of them a
+ * full row.  With admission on, an id gets a row only once it has been ASKED FOR min_count times
+ * while absent.  The counts live in a count-min sketch of SWPS_ADMIT_DEPTH x width u32 cells in
+ * HBM beside the shard.  The gate is deterministic: everything below is the whole rule, every
+ * step is integer arithmetic, and a host model written from it reproduces the table bit for bit.
+ *
+ * Cell rule: cell(j, key) = j * width + (fmix64(key ^ fmix64(cfg.seed + j)) & (width - 1)) for
+ *   j = 0 .. SWPS_ADMIT_DEPTH - 1, an index into cells[SWPS_ADMIT_DEPTH][width] (fmix64: swps_fmix64,
+ *   sums mod 2^64, cfg.seed as given at swps_table_create).
+ *
+ * The gate: swps_lookup and swps_lookup_bag with insert = 1 on a LOCAL table with admission on.  Let
+ *   U be the distinct non-padding keys of the call in first-occurrence order and c[u] each key's
+ *   number of non-padding occurrences (a key twice in a bag counts twice).
+ *     1. A0 = the keys of U the shard lacks.  Keys it holds are untouched by the gate.
+ *     2. ADD: for every key of A0 and every j,
+ *          cells[cell(j, key)] = min(2^32 - 1, cells[cell(j, key)] + min(c[u], min_count))
+ *        the saturating sum over all of A0, whatever order the device runs in.
+ *     3. TEST, after the whole of step 2 (so the keys of one call see each other's counts):
+ *          est(key) = min over j of cells[cell(j, key)];  admitted iff est(key) >= min_count.
+ *        A count-min estimate never under-counts: a key asked for min_count times while absent IS
+ *        admitted; collisions can only admit a key early, never refuse one.
+ *     4. The admitted keys, in first-occurrence order, are inserted exactly as swps_pull of that
+ *        list would: same init_param (an SWPS_INIT_FLCG table draws in admitted first-occurrence
+ *        order), same SWPS_E_OOM latch, and under a ceiling the growth bound counts the ADMITTED
+ *        keys, not the distinct ones.  The host has to know that count first: a gated lookup
+ *        makes one more host read plus stream synchronise than an ungated one.
+ *     5. A refused key reads as a zero value with d_found = 0 and latches nothing; in a bag it is a
+ *        member that contributes zero (and counts in the mean), as insert = 0 defines for absent
+ *        keys.  ~0 stays the SWPS_E_BADKEY (swps_lookup) / the skipped padding (swps_lookup_bag).
+ *     6. tested += |A0|, admitted += the keys that passed step 3, refused += the rest.
+ *   So a key repeated >= min_count times in one call is admitted in that call, and a key seen once
+ *   per call is admitted on call number min_count (or earlier, through collisions).
+ *   swps_push_dup and swps_push_bag on a table with admission on SKIP a key the shard lacks and
+ *   latch nothing: it is a refused id's gradient.  With admission off they latch SWPS_E_BADKEY.
+ *   NOT gated (they insert unconditionally, as the parameter-server path must): swps_pull / _h /
+ *   _async, swps_push*, swps_assign / _h, swps_load, swps_restore, the app contexts.  The _h forms
+ *   of lookup and push behave as the device forms.  More than 2^31 - 1 distinct keys in one gated
+ *   call -> SWPS_E_UNSUPPORTED.
+ *
+ * swps_table_set_admission(t, min_count, width): min_count <= 1 turns admission OFF and frees the
+ *   sketch (the default: every call then behaves exactly as without this section).  Otherwise width
+ *   must be a power of two in [2^6, 2^30], else SWPS_E_CFG (checked first, before the table is
+ *   looked at); SWPS_ADMIT_DEPTH x width zeroed cells are allocated (SWPS_E_OOM leaves admission
+ *   off).  Calling it again reallocates and zeroes the cells and zeroes the three counters.
+ *   Synchronises the device, as swps_table_reserve does.  Turning admission on for a routed table
+ *   returns SWPS_E_UNSUPPORTED, and so does swps_table_route on a table with admission on.
+ * The sketch is not part of the rows: growth, swps_table_reserve / _shrink, swps_erase, swps_prune,
+ *   swps_save / swps_restore and the snapshot checksum leave it alone and are left alone by it.  An
+ *   ERASED key keeps its old counts, so it may be re-admitted at its next lookup;
+ *   swps_admission_decay(t, 32) is the reset.
+ * swps_admission_info: out6 = {min_count (0: off), width, depth, tested, admitted, refused}.
+ * swps_admission_decay(t, shift): every cell >>= shift for shift in 1..31, 32 clears the cells;
+ *   anything else SWPS_E_CFG.  The counters are kept.
+ * swps_admission_cells(t, cells, cap, n): the cells as a host array [depth][width]; *n (may be NULL)
+ *   = depth x width; cap < that (or cells NULL) -> SWPS_E_CFG with *n set.  swps_admission_load puts
+ *   such an array back; n must be depth x width, else SWPS_E_CFG.  Together they checkpoint the
+ *   sketch.  decay / cells / load synchronise the device and need admission on (SWPS_E_STATE). */
+#define SWPS_ADMIT_DEPTH 4
+int swps_table_set_admission(swps_table *t, uint32_t min_count, uint64_t width);
+int swps_admission_info(swps_table *t, uint64_t *out6);
+int swps_admission_decay(swps_table *t, int32_t shift);
+int swps_admission_cells(swps_table *t, uint32_t *cells, uint64_t cap, uint64_t *n);
+int swps_admission_load(swps_table *t, const uint32_t *cells, uint64_t n);
+
 /* Overwrite / read full rows (table dtype, d_rows[n][row elems]). */
 int swps_assign(swps_table *t, const uint64_t *d_keys, uint64_t n, const void *d_rows);
 int swps_export(swps_table *t, const uint64_t *d_keys, uint64_t n, void *d_rows);

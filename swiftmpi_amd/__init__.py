@@ -141,9 +141,11 @@ class Table:
     """One HBM parameter shard (SparseTable + server access methods)."""
 
     def __init__(self, layout="w2v", dim=100, capacity=1 << 20, dtype="f32", learning_rate=0.7, fudge=1e-6,
-                 init="hash", seed=0, device=0, push_rule="adagrad", max_capacity=None):
+                 init="hash", seed=0, device=0, push_rule="adagrad", max_capacity=None, admit_min_count=None,
+                 admit_width=1 << 20):
         """max_capacity: the ceiling under which inserts grow the shard by themselves (None / 0:
-        the capacity is fixed, as in the reference-sized default); `capacity` is the starting size."""
+        the capacity is fixed, as in the reference-sized default); `capacity` is the starting size.
+        admit_min_count / admit_width: `set_admission` at creation (None: every new id gets a row)."""
         inits = {"hash": capi.INIT_HASH, "zero": capi.INIT_ZERO, "flcg": capi.INIT_FLCG}
         rules = {"adagrad": capi.PUSH_ADAGRAD, "sgd": capi.PUSH_SGD}
         layouts = {"w2v": capi.LAYOUT_W2V, "lr": capi.LAYOUT_LR}
@@ -164,6 +166,8 @@ class Table:
         self._deps = weakref.WeakSet()  # app contexts bound to this shard: closed first
         if max_capacity:
             self.set_max_capacity(max_capacity)
+        if admit_min_count is not None:
+            self.set_admission(admit_min_count, admit_width)
 
     def close(self):
         if getattr(self, "h", None):
@@ -252,6 +256,59 @@ class Table:
         if keys < 0:
             raise ValueError("keys must be >= 0")
         check(capi.lib().swps_table_shrink(self.h, keys))
+
+    # ---- admission by count (swps_table_set_admission / swps_admission_*) ----
+    def set_admission(self, min_count, width=1 << 20):
+        """Gate the inserting lookups (`lookup`, `lookup_bag`, the nn modules) on a count-min
+        sketch of 4 x width counters beside the shard: an id gets a row only once it has been asked
+        for `min_count` times while absent; until then it reads as a zero row (found = 0) and its
+        gradient is skipped.  min_count <= 1 (or None) turns the gate off and frees the sketch.
+        width: a power of two in [2^6, 2^30].  Calling it again zeroes the sketch and the counters.
+        `pull`, `assign`, `load` and `restore` are never gated; not available on a routed table."""
+        min_count = 0 if min_count is None else min_count
+        for name, v in (("min_count", min_count), ("width", width)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError("%s must be an integer" % name)
+        min_count, width = int(min_count), int(width)
+        if min_count < 0 or min_count >= 1 << 32:
+            raise ValueError("min_count must be in [0, 2^32)")
+        if min_count > 1 and (width < 1 << 6 or width > 1 << 30 or width & (width - 1)):
+            raise ValueError("width must be a power of two in [2^6, 2^30], not %d" % width)
+        check(capi.lib().swps_table_set_admission(self.h, min_count, width))
+
+    def admission(self):
+        """The gate's settings and counters: min_count (0: off), width, depth, and the absent keys
+        tested / admitted / refused by the inserting lookups since `set_admission`."""
+        out = np.zeros(6, dtype=np.uint64)
+        check(capi.lib().swps_admission_info(self.h, ptr(out)))
+        return dict(zip(["min_count", "width", "depth", "tested", "admitted", "refused"], (int(x) for x in out)))
+
+    def admission_decay(self, shift=1):
+        """Every counter of the sketch >>= shift (1..31); 32 clears it.  Ages old counts, so an id
+        has to keep coming to be admitted."""
+        if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)):
+            raise TypeError("shift must be an integer")
+        if not 1 <= int(shift) <= 32:
+            raise ValueError("shift must be in 1..32 (32 clears)")
+        check(capi.lib().swps_admission_decay(self.h, int(shift)))
+
+    def admission_cells(self):
+        """The sketch as a numpy uint32 [4, width] array (a checkpoint: `admission_load` puts it back)."""
+        width = self.admission()["width"]
+        out = np.zeros((capi.ADMIT_DEPTH, max(width, 1)), dtype=np.uint32)
+        n = ctypes.c_uint64()
+        check(capi.lib().swps_admission_cells(self.h, ptr(out), out.size, ctypes.byref(n)))
+        return out
+
+    def admission_load(self, cells):
+        """Overwrite the sketch with a uint32 [4, width] array of the width set by `set_admission`."""
+        a = np.asarray(cells)
+        if a.dtype != np.uint32:
+            raise TypeError("cells must be uint32, not %s" % a.dtype)
+        if a.ndim != 2 or a.shape[0] != capi.ADMIT_DEPTH:
+            raise ValueError("cells must have the shape [%d, width]" % capi.ADMIT_DEPTH)
+        a = np.ascontiguousarray(a)
+        check(capi.lib().swps_admission_load(self.h, ptr(a), a.size))
 
     def pull(self, keys):
         """keys: int64/uint64 CUDA tensor of distinct keys -> [n, pull_elems] tensor."""
@@ -362,7 +419,9 @@ class Table:
         shape -> [*keys.shape, pull_elems] in the table dtype, on torch's current stream; a numpy
         array -> the host form (wire types: W2V fp64, LR fp32).  insert=True inserts every absent
         distinct key once, as `pull` of the distinct keys would; insert=False returns zeros for
-        absent keys and padding.  return_found: also the per-position flags (uint8 / bool)."""
+        absent keys and padding.  return_found: also the per-position flags (uint8 / bool).  With
+        admission on (`set_admission`) insert=True inserts only the ids that have come often enough;
+        a refused id reads as zeros with found = 0."""
         lib = capi.lib()
         if hasattr(keys, "data_ptr"):
             import torch
@@ -389,7 +448,7 @@ class Table:
         [*keys.shape, push_elems], fp32 or fp64 (LR tables: fp32), never cast on the host.  CUDA
         tensors run on torch's current stream; numpy arrays take the host form (wire types).
         Padding (-1) positions are skipped; a key the table lacks raises SWPS_E_BADKEY after the
-        other keys were applied."""
+        other keys were applied (with admission on it is a refused id's gradient and only skipped)."""
         if reduce not in self._REDUCE:
             raise ValueError("reduce is 'sum' or 'mean'")
         lib = capi.lib()

@@ -26,6 +26,7 @@ NEAREST_MAX_K, NEAREST_MAX_EXCL = 64, 8
 REDUCE_SUM, REDUCE_MEAN = 0, 1
 DUP_CHUNK = 128
 BAG_SUM, BAG_MEAN = 0, 1
+ADMIT_DEPTH = 4
 COMM_ID_BYTES = 128
 
 # swps_transport callbacks (host all-gather / all-to-all-v)
@@ -105,6 +106,11 @@ PROTOS = {
     "swps_push_bag": (ctypes.c_int, [_p, _p, _u64, _p, _u64, _p, _i32, _p, _i32, ctypes.c_double, _p]),
     "swps_lookup_bag_h": (ctypes.c_int, [_p, _p, _u64, _p, _u64, _p, _i32, _i32, _p]),
     "swps_push_bag_h": (ctypes.c_int, [_p, _p, _u64, _p, _u64, _p, _i32, _p, ctypes.c_double]),
+    "swps_table_set_admission": (ctypes.c_int, [_p, ctypes.c_uint32, _u64]),
+    "swps_admission_info": (ctypes.c_int, [_p, _p]),
+    "swps_admission_decay": (ctypes.c_int, [_p, _i32]),
+    "swps_admission_cells": (ctypes.c_int, [_p, _p, _u64, ctypes.POINTER(_u64)]),
+    "swps_admission_load": (ctypes.c_int, [_p, _p, _u64]),
     "swps_comm_unique_id": (ctypes.c_int, [_p]),
     "swps_comm_bootstrap_tcp": (ctypes.c_int, [ctypes.c_char_p, _i32, _i32, _i32, _i32, _p]),
     "swps_comm_create_rccl": (ctypes.c_int, [_p, _i32, _i32, _i32, ctypes.POINTER(_p)]),

@@ -11,6 +11,7 @@
 // (bag, chunk) items by POSITION, so the items follow from the offsets alone (no key is read).
 // No kernel here waits on another thread: every dependency is a kernel boundary.
 #include "swps_dup.h"
+#include "swps_admit.h"
 
 using namespace swps;
 
@@ -391,14 +392,19 @@ int swps_lookup_bag(swps_table *t, const uint64_t *d_keys, uint64_t n, const uin
   BagScratch B;
   Runs R;
   uint64_t *uniq = nullptr;
-  uint32_t *inv = nullptr;
+  uint32_t *inv = nullptr, *count = nullptr;
+  const bool gated = insert && !t->comm && t->adm_min > 1;  // admission by count
   if (nbags) SWPS_TRY(bag_runs(t, d_keys, n, d_offsets, nbags, false, B, R, s));  // refuses bad offsets here
   if (n) {
     SWPS_TRY(t->dup[B_UNIQ].ensure((R.nu + 1) * 8));
     SWPS_TRY(t->dup[B_INV].ensure(n * 4));
     uniq = t->dup[B_UNIQ].as<uint64_t>();
     inv = t->dup[B_INV].as<uint32_t>();
-    SWPS_TRY(rank_runs(t, R, uniq, inv, nullptr, s));
+    if (gated) {
+      SWPS_TRY(t->adm_cnt.ensure((R.nu + 1) * 4));
+      count = t->adm_cnt.as<uint32_t>();
+    }
+    SWPS_TRY(rank_runs(t, R, uniq, inv, count, s));
   }
   if (t->comm) {  // collective: the routed pull of the distinct keys, pooled through inv
     const size_t cb = (size_t)t->pull_elems * t->esize;
@@ -420,8 +426,9 @@ int swps_lookup_bag(swps_table *t, const uint64_t *d_keys, uint64_t n, const uin
     uint32_t *row_u = t->dup[B_ROWS].as<uint32_t>();
     if (insert) {
       // exactly swps_lookup's insert of the distinct list; a failure (table full) still leaves the
-      // found keys' rows, and the keys without one pool as zero rows
-      rc = table_find_or_insert(t, uniq, R.nu, row_u, s);
+      // found keys' rows, and the keys without one pool as zero rows; gated: the admitted keys only,
+      // a refused key is such a zero row
+      rc = gated ? admit_insert(t, uniq, count, R.nu, row_u, s) : table_find_or_insert(t, uniq, R.nu, row_u, s);
       if (rc != SWPS_OK && rc != SWPS_E_OOM && rc != SWPS_E_BADKEY) return rc;
       if (rc != SWPS_OK) msg = swps_last_error();
     } else {
@@ -478,7 +485,12 @@ int swps_push_bag(swps_table *t, const uint64_t *d_keys, uint64_t n, const uint6
   if (R.nu) {
     SWPS_TRY(t->dup[B_ROWS].ensure(R.nu * 4));
     uint32_t *row_r = t->dup[B_ROWS].as<uint32_t>();
-    SWPS_TRY(table_lookup(t, rkeys, R.nu, row_r, s));  // an unknown key: latched, its run skipped
+    // an unknown key: latched, its run skipped; with admission on it is a refused id's gradient
+    // and only skipped
+    if (t->adm_min > 1)
+      SWPS_TRY(table_probe(t, rkeys, R.nu, row_r, s));
+    else
+      SWPS_TRY(table_lookup(t, rkeys, R.nu, row_r, s));
     SWPS_TRY((reduce_runs<true, true>(t, R, d_bag_grads, gdtype, row_r, nullptr, SWPS_REDUCE_SUM, scale, s, &bag)));
   }
   return table_check_error(t, s);

@@ -1347,6 +1347,9 @@ int swps_table_route(swps_table *t, swps_comm *c, int32_t frag_num) {
   if (!t || !c) return fail(SWPS_E_CFG, "null argument");
   if (c->device != t->cfg.device) return fail(SWPS_E_CFG, "communicator and table are on different devices");
   if (frag_num < c->world) return fail(SWPS_E_CFG, "frag_num < world (hashfrag.h divides by frag_num / world)");
+  if (t->adm_min > 1)
+    return fail(SWPS_E_UNSUPPORTED, "swps_table_route on a table with admission on (swps_table_set_admission): the "
+                                    "counts would have to travel with the routed pull");
   SWPS_HIP(hipSetDevice(t->cfg.device));
   std::vector<uint32_t> map(frag_num);
   SWPS_TRY(swps_hashfrag_table(frag_num, c->world, map.data()));

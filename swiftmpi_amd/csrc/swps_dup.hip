@@ -11,6 +11,7 @@
 // No kernel here waits on another thread: every dependency is a kernel boundary.  The kernels and
 // the host helpers live in swps_dup.h, which the pooled calls (swps_bag.hip) share.
 #include "swps_dup.h"
+#include "swps_admit.h"
 
 using namespace swps;
 
@@ -43,14 +44,19 @@ int swps_lookup(swps_table *t, const uint64_t *d_keys, uint64_t n, int32_t inser
   hipStream_t s = stream ? (hipStream_t)stream : t->stream;
   Runs R;
   uint64_t *uniq = nullptr;
-  uint32_t *inv = nullptr;
+  uint32_t *inv = nullptr, *count = nullptr;
+  const bool gated = insert && !t->comm && t->adm_min > 1;  // admission by count
   if (n) {
     SWPS_TRY(sorted_runs(t, d_keys, n, s, false, R));
     SWPS_TRY(t->dup[B_UNIQ].ensure((R.nu + 1) * 8));
     SWPS_TRY(t->dup[B_INV].ensure(n * 4));
     uniq = t->dup[B_UNIQ].as<uint64_t>();
     inv = t->dup[B_INV].as<uint32_t>();
-    SWPS_TRY(rank_runs(t, R, uniq, inv, nullptr, s));
+    if (gated) {
+      SWPS_TRY(t->adm_cnt.ensure((R.nu + 1) * 4));
+      count = t->adm_cnt.as<uint32_t>();
+    }
+    SWPS_TRY(rank_runs(t, R, uniq, inv, count, s));
   }
   uint32_t *pad_flag = insert ? t->counters.as<uint32_t>() + 1 : nullptr;
   if (t->comm) {  // collective: the routed pull of the distinct keys, scattered through inv
@@ -66,8 +72,9 @@ int swps_lookup(swps_table *t, const uint64_t *d_keys, uint64_t n, int32_t inser
   std::string msg;
   if (insert) {
     // exactly swps_pull's insert of the distinct list (growth, init_param, latches); a failure
-    // (table full) still leaves the found keys' rows, which are returned as swps_pull returns them
-    rc = table_find_or_insert(t, uniq, R.nu, row_u, s);
+    // (table full) still leaves the found keys' rows, which are returned as swps_pull returns them;
+    // gated: the same insert of the admitted keys only, a refused key reads as an absent one
+    rc = gated ? admit_insert(t, uniq, count, R.nu, row_u, s) : table_find_or_insert(t, uniq, R.nu, row_u, s);
     if (rc != SWPS_OK && rc != SWPS_E_OOM && rc != SWPS_E_BADKEY) return rc;
     if (rc != SWPS_OK) msg = swps_last_error();
   } else {
@@ -111,7 +118,12 @@ int swps_push_dup(swps_table *t, const uint64_t *d_keys, uint64_t n, const void 
   if (R.nu) {
     SWPS_TRY(t->dup[B_ROWS].ensure(R.nu * 4));
     uint32_t *row_r = t->dup[B_ROWS].as<uint32_t>();
-    SWPS_TRY(table_lookup(t, rkeys, R.nu, row_r, s));  // an unknown key: latched, its run skipped
+    // an unknown key: latched, its run skipped; with admission on it is a refused id's gradient
+    // and only skipped
+    if (t->adm_min > 1)
+      SWPS_TRY(table_probe(t, rkeys, R.nu, row_r, s));
+    else
+      SWPS_TRY(table_lookup(t, rkeys, R.nu, row_r, s));
     SWPS_TRY(reduce_runs<true>(t, R, d_grads, gdtype, row_r, nullptr, reduce, scale, s));
   }
   return table_check_error(t, s);

@@ -307,6 +307,14 @@ struct swps_table {
   // flags, their prefix sum with its temporary storage, the compaction's (mover, hole) pairs
   swps::DevMem er_rows, er_dead, er_scan, er_tmp, er_src, er_dst;
   uint64_t er_last = 0;  // the local shard's count of the last routed erase round (route_round)
+  // admission by count (swps_table_set_admission, swps_admit.hip): the count-min
+  // sketch beside the shard, never part of the rows; grow-only per-call buffers (the distinct keys'
+  // occurrence counts; the flags, their scan, the admitted keys / indices / rows; the scan's storage)
+  uint32_t adm_min = 0;       // 0: off, else the min_count (> 1)
+  uint64_t adm_width = 0;     // cells per sketch row, a power of two
+  swps::DevMem adm_cells;     // [SWPS_ADMIT_DEPTH][adm_width] u32
+  swps::DevMem adm_cnt, adm_buf, adm_scan;
+  uint64_t adm_stat[3] = {0, 0, 0};  // tested, admitted, refused
 };
 
 namespace swps {

@@ -49,7 +49,9 @@ class SparseEmbedding(torch.nn.Module):
     tables: [h | v], 2 * dim values; LR tables: the weight) through `Table.lookup(insert=True)`:
     ids the table lacks are inserted with its init rule.  The id -1 is padding: a zero row, no
     gradient.  The rows are updated by the table's push rule during `backward()` (see the module
-    docstring); `maximize` pushes the gradient itself instead of its negation."""
+    docstring); `maximize` pushes the gradient itself instead of its negation.  On a table with
+    admission on (`Table.set_admission`) a refused id reads as a zero row and its backward is
+    skipped."""
 
     def __init__(self, table, maximize=False):
         super().__init__()
@@ -99,7 +101,9 @@ class SparseEmbeddingBag(torch.nn.Module):
     As `SparseEmbedding`: no torch parameters, the rows are updated by the table's push rule DURING
     `backward()` (`Table.push_bag` with scale -1, or +1 with `maximize`), every distinct id takes
     one step with its terms summed in fp64 in a defined order, so a backward pass is
-    bit-reproducible; calling `backward()` twice on one graph applies two steps."""
+    bit-reproducible; calling `backward()` twice on one graph applies two steps.  On a table with
+    admission on (`Table.set_admission`) a refused id reads as a zero row (a member that still
+    counts in the mean) and its backward is skipped."""
 
     def __init__(self, table, mode="sum", maximize=False, include_last_offset=False):
         super().__init__()
