@@ -117,6 +117,8 @@ class AdmitModel:
     def decay(self, shift):
         assert 1 <= shift <= 32
         self.cells = np.zeros_like(self.cells) if shift == 32 else self.cells >> np.uint32(shift)
+        # the exact counts age with the cells: (a + b) >> s >= (a >> s) + (b >> s), so "never under-counts" still holds
+        self.true_count = {k: (0 if shift == 32 else v >> shift) for k, v in self.true_count.items()}
 
     def counters(self):
         return dict(tested=self.tested, admitted=self.admitted, refused=self.refused)

@@ -62,11 +62,19 @@ def int_case(D, nrows, nq, seed):
 
 
 def f32_scores(rows, q, metric):
-    """np.float32(dot) / np.sqrt(np.float32(r.r)) (0 for a zero row) on exactly representable sums."""
-    dot = (q.astype(np.float64) @ rows.T).astype(np.float32)
-    if metric == "dot":
-        return dot
-    n2 = (rows * rows).sum(1).astype(np.float32)
+    """np.float32(dot) / np.sqrt(np.float32(r.r)) (0 for a zero row) on exactly representable sums.
+    Non-finite rows or queries (test_non_finite_scores derives why this is the fp32 chain's value
+    there too) take elementwise IEEE products and sums, not a BLAS call whose handling of inf * 0 is
+    its own business."""
+    q64 = q.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        if np.isfinite(rows).all() and np.isfinite(q64).all():
+            dot = (q64 @ rows.T).astype(np.float32)
+        else:
+            dot = (q64[:, None, :] * rows[None, :, :]).sum(2).astype(np.float32)
+        if metric == "dot":
+            return dot
+        n2 = (rows * rows).sum(1).astype(np.float32)
     with np.errstate(divide="ignore", invalid="ignore"):
         s = dot / np.sqrt(n2)[None, :]
     assert s.dtype == np.float32
@@ -367,3 +375,159 @@ def test_routed_two_ranks(lib, gpu):
     print(r.stdout[-6000:])
     print("\n".join(ln for ln in r.stderr.splitlines() if "rank0" in ln or "Error" in ln)[-6000:])
     assert r.returncode == 0 and "NEAREST OK" in r.stdout
+
+
+# ---- 7. non-finite scores: the order's NaN class, infinities, inf * 0, an overflowing r.r ---------
+BIG = 1.5 * 2.0 ** 63  # 1.38e19, exact in fp32; BIG * BIG = 2.25 * 2^126 is finite, twice that is not
+NF_ROWS, NF_NQ = 200, 35
+NF_FIRST = 150  # the doctored rows: clear of int_case's duplicated rows (0..39) and its zero row (100)
+NF_ZPOS = (1, 4)  # where query 0 holds zeros and the "inf0" row its infinities
+
+
+@functools.lru_cache(maxsize=None)
+def nonfinite_case(D):
+    """int_case with a dozen doctored rows (name -> index in `names`) and three doctored queries:
+    query 0 holds 0 at NF_ZPOS, query 33 a NaN, query 34 a +inf."""
+    keys, rows, q = int_case(D, NF_ROWS, NF_NQ, seed=900 + D)
+    nan, inf = np.nan, np.inf
+    names = {}
+
+    def put(name, values, fill=None):  # values: {position: value}; fill: the other elements (None: the integers)
+        i = names[name] = NF_FIRST + len(names)
+        if fill is not None:
+            rows[i] = fill
+        for p, v in values.items():
+            rows[i, p] = v
+
+    put("one_nan", {1: nan})
+    put("tail_nan", {D - 1: nan})
+    put("all_nan", {}, fill=nan)
+    put("pinf", {0: inf})
+    put("pinf_twin", {0: inf})
+    rows[names["pinf_twin"]] = rows[names["pinf"]]  # equal infinite scores: the smaller key first
+    put("ninf", {2: -inf})
+    put("both_inf", {0: inf, 3: -inf})
+    put("inf0", {p: inf for p in NF_ZPOS})
+    put("all_pinf", {}, fill=inf)
+    for name, vals in (("big_even_odd", {0: BIG, 3: BIG}), ("big_even", {0: BIG, 2: BIG}), ("big_mixed", {1: -BIG, 4: BIG})):
+        put(name, vals, fill=0)
+    q[0, list(NF_ZPOS)] = 0
+    q[33, 2] = nan
+    q[34, 0] = inf
+    return keys, rows, q, names
+
+
+def check_total_order(gk, gs):
+    """The contract's order read off the answer alone: numbers (higher first, ties by smaller key),
+    then NaN scores by ascending key, then the ~0 / -inf padding."""
+    for i in range(gk.shape[0]):
+        pad = gk[i] == EMPTY
+        nan = np.isnan(gs[i]) & ~pad
+        cls = np.where(pad, 2, np.where(nan, 1, 0))
+        assert np.all(np.diff(cls) >= 0), (i, cls.tolist())
+        assert np.all(np.isneginf(gs[i][pad]))
+        nk = gk[i][nan]
+        assert np.all(nk[1:] > nk[:-1]), (i, nk.tolist())
+        num_s, num_k = gs[i][cls == 0], gk[i][cls == 0]
+        assert np.all((num_s[1:] < num_s[:-1]) | ((num_s[1:] == num_s[:-1]) & (num_k[1:] > num_k[:-1]))), i
+
+
+def check_scores(gk, gs, wk, ws, what):
+    assert np.array_equal(gk, wk), what
+    nan = np.isnan(ws)
+    assert np.array_equal(np.isnan(gs), nan), what
+    assert np.array_equal(gs[~nan], ws[~nan]), what
+
+
+@pytest.mark.parametrize("metric", ["dot", "cos"])
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+@pytest.mark.parametrize("D", [5, 32, 100])
+def test_non_finite_scores(lib, gpu, monkeypatch, D, dtype, metric):
+    """NaN and infinite values in rows and queries, which the suite's other query tests never hold.
+
+    The reference, from IEEE 754 alone.  A score is the chain acc = fma(r[k], q[k], acc) over k from
+    acc = 0 (the padded k tail adds fma(0, 0, acc) = acc), under cos divided by sqrt(r.r), r.r two such
+    chains (even and odd k) added.  Every finite entry is a small integer, so as long as acc is finite
+    it is exact, and
+      - a NaN operand makes the product NaN and every later acc NaN;
+      - inf * 0 is NaN (the "inf0" row against query 0; the +inf query against rows holding 0 there);
+      - +inf and -inf terms in one chain: inf + -inf is NaN, whichever comes first ("both_inf" against
+        a query whose elements there have one sign; of opposite signs the two terms are one infinity);
+      - infinities of one sign only: that infinity ("pinf", "ninf", "all_pinf"), and equal infinite
+        scores are a tie that the smaller key wins ("pinf_twin");
+      - cos: r.r of a row with a NaN is NaN and s / NaN is NaN; with an infinity r.r = +inf, sqrt
+        gives +inf, and an infinite dot / +inf is NaN while a finite one gives a signed zero, which
+        compares equal to the zero row's 0 (a tie by key);
+      - the "big" rows: BIG^2 = 2.25 * 2^126 is finite in fp32 and the second such term overflows to
+        +inf, in one chain ("big_even") or at the final even + odd addition ("big_even_odd"); their
+        dots (3 q_a +- 3 q_b) * 2^62 are exact (the other elements are 0), so cos gives +-0 and dot
+        the largest finite scores of the table.
+    The order of the additions never decides the CLASS of the result (NaN, +inf, -inf, finite), and
+    the finite results are exact, so elementwise fp64 products summed in any order and rounded to
+    fp32 once (f32_scores) are the chain's values; the NaN's sign and payload are not compared.
+    r.r cast from fp64 overflows to +inf exactly where the fp32 chain does: all its terms are >= 0."""
+    from swiftmpi_amd.evaluate import topk_order
+    keys, rows, q, names = nonfinite_case(D)
+    part = "v" if D != 32 else "h"
+    t = fill(lib, D, keys, rows, part, dtype)
+    ref = f32_scores(rows, q, metric)
+    # the derivation above, spot-checked on the reference before it judges the kernel
+    col = {n: ref[:, i] for n, i in names.items()}
+    assert np.isnan(col["one_nan"]).all() and np.isnan(col["all_nan"]).all() and np.isnan(col["tail_nan"]).all()
+    assert np.isnan(col["inf0"][0]) and np.isnan(ref[33]).sum() >= NF_ROWS - 1
+    same = q[:33, 0] * q[:33, 3] >= 0  # inf * q0 and -inf * q3 of opposite signs (or an inf * 0)
+    assert same.any() and not same.all()
+    assert np.array_equal(np.isnan(col["both_inf"][:33]), same if metric == "dot" else np.ones(33, dtype=bool))
+    if metric == "dot":
+        fin = q[:33, 0] != 0
+        assert np.array_equal(col["pinf"][:33][fin], np.where(q[:33, 0][fin] > 0, np.inf, -np.inf).astype(np.float32))
+        assert np.array_equal(col["big_even_odd"][:33], ((3 * q[:33, 0] + 3 * q[:33, 3]) * 2.0 ** 62).astype(np.float32))
+    else:
+        assert np.isnan(col["pinf"][:33][q[:33, 0] != 0]).all()  # inf / inf
+        assert not col["big_even"][:33].any() and not col["big_even_odd"][:33].any()  # finite / inf = +-0
+        assert not ref[33, NF_ROWS // 2] and not np.isnan(ref[33, NF_ROWS // 2])  # the zero row under a NaN query
+    rng = np.random.default_rng(D)
+    nan_rows = keys[[names["one_nan"], names["all_nan"], names["tail_nan"], names["both_inf"]]]
+    excl = np.stack([rng.choice(keys, 3) for _ in range(NF_NQ)])
+    excl[:, 2] = EMPTY
+    excl[::2, 0] = nan_rows[0]
+    excl[1::3, 1] = nan_rows[3]
+    # 40 candidates: every doctored row, plain rows, and keys the table lacks; k = 64 then lists the
+    # numbers, the NaN scores and the padding of one query side by side
+    cand = np.concatenate([keys[NF_FIRST:NF_FIRST + len(names)], rng.choice(keys[:NF_FIRST], 23, replace=False),
+                           make_keys(rng, 5) + np.uint64(1)])
+    twin = fill(lib, D, keys, rows, part, dtype, order=rng.permutation(len(keys)), capacity=777)
+    seen_nan_before_pad = False
+    for batch in (None, "32"):
+        if batch:
+            monkeypatch.setenv("SWPS_NEAREST_BATCH", batch)  # 35 queries: two batches
+        for k in (1, 10, 64):
+            for e, c in ((None, None), (excl, cand)):
+                what = (D, dtype, metric, k, e is not None, batch)
+                wk, ws = topk_order(ref, keys, k, e, c)
+                gk, gs = t.nearest(q, k=k, part=part, metric=metric, exclude=e, candidates=c)
+                check_scores(gk, gs, wk, ws, what)
+                check_total_order(gk, gs)
+                tk, ts = twin.nearest(q, k=k, part=part, metric=metric, exclude=e, candidates=c)
+                assert np.array_equal(tk, gk) and np.array_equal(ts.view(np.uint32), gs.view(np.uint32)), what
+                seen_nan_before_pad |= bool(((gk[:, :-1] != EMPTY) & np.isnan(gs[:, :-1]) & (gk[:, 1:] == EMPTY)).any())
+    assert seen_nan_before_pad
+    # the device form, and an analogy whose operand rows hold the non-finite values
+    dk, ds = as_np(*t.nearest(torch.as_tensor(q, device=gpu), k=10, part=part, metric=metric))
+    wk, ws = topk_order(ref, keys, 10)
+    check_scores(dk, ds, wk, ws, "device")
+    ia = np.stack([rng.choice(len(keys), 3, replace=False) for _ in range(NF_NQ)])
+    nf = len(names) - 3  # not the "big" rows: BIG next to small integers in one query is not exact in fp32
+    ia[:nf, 1] = np.arange(NF_FIRST, NF_FIRST + nf)
+    ia[:nf, 0], ia[:nf, 2] = 3, 7
+    r32 = rows.astype(np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        aq = (r32[ia[:, 1]] - r32[ia[:, 0]]) + r32[ia[:, 2]]
+        wk, ws = topk_order(f32_scores(rows, aq, metric), keys, 10, keys[ia])
+    gk, gs = t.analogy(keys[ia], k=10, part=part, metric=metric)
+    check_scores(gk, gs, wk, ws, "analogy")
+    check_total_order(gk, gs)
+    tk, ts = twin.analogy(keys[ia], k=10, part=part, metric=metric)
+    assert np.array_equal(tk, gk) and np.array_equal(ts.view(np.uint32), gs.view(np.uint32))
+    t.close()
+    twin.close()
